@@ -68,6 +68,33 @@ def make_input(batch, h, w, dev, seed):
     return torch.nn.functional.pad(x, (0, wn, 0, hn), mode="reflect").to(dev).contiguous()   # inference_fdn_lolblur.py:60-62
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6     # --dump-outputs: every .npy file of one run together, headers included
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(outs, out_dir, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each array of `outs` ({name: tensor}) as out_dir/<name>.npy, float64 kept, every other dtype as float32, so
+    that two builds run with the same arguments can be compared output for output.  An array larger than its share of `limit` is
+    stored as a fixed sample: its flattened elements at the positions torch.randperm(numel) draws first from a generator seeded
+    DUMP_SAMPLE_SEED, in ascending order - the same positions in every run and every build.  Returns {name: description}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = limit // max(len(outs), 1) - 1024                   # room for the .npy header
+    rec = {}
+    for name, t in outs.items():
+        t = t.detach().cpu()
+        t = t if t.dtype == torch.float64 else t.float()
+        rec[name] = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", "")}
+        if t.numel() * t.element_size() > share:
+            k = share // t.element_size()
+            pos = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(DUMP_SAMPLE_SEED))[:k].sort().values
+            t = t.reshape(-1)[pos]
+            rec[name]["sample"] = {"elements": k, "seed": DUMP_SAMPLE_SEED,
+                                   "positions": "torch.randperm(numel, generator seeded `seed`)[:elements], ascending, into the flattened array"}
+        np.save(os.path.join(out_dir, name + ".npy"), t.contiguous().numpy())
+    return rec
+
+
 def _iv(v):
     """ctypes argument -> Python int (plain ints pass through, c_long / c_int carry .value)."""
     return v.value if hasattr(v, "value") else v
@@ -665,7 +692,13 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU / gloo rehearsal of the launcher, sharding, scatter / gather and timing protocol with a stand-in "
                          "forward (tests/test_multirank_cpu.py); measures nothing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step (rank 0: the gathered global batch "
+                         "when the scatter / gather is timed) as DIR/<name>.npy, float32 or float64, at most 64 MB in all (a larger "
+                         "output as a fixed seeded sample, see dump_outputs); the inputs depend on the arguments only")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(launch_ranks(a.gpus, sys.argv[1:]))       # parent: no GPU call before or after this line
@@ -776,6 +809,7 @@ def main():
         sync()
 
     host_s = [0.0]
+    last_out = [None]
 
     def timed(with_sg, steps):
         barrier()
@@ -784,7 +818,7 @@ def main():
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
         for _ in range(steps):
-            step(with_sg)
+            last_out[0] = step(with_sg)
         if not a.dry_run:
             e1.record()
         host_s[0] = time.perf_counter() - t0               # host time to ISSUE the K steps (the GPU is still running)
@@ -803,6 +837,10 @@ def main():
             dt = timed(sg, a.steps)                                    # THE measurement: exactly K steps
     else:
         dt = timed(sg, a.steps)
+    dumped = None
+    if a.dump_outputs and rank == 0:                                   # before anything else replays the graph into the same output tensor
+        out = torch.cat(root_out) if sg else last_out[0]
+        dumped = dump_outputs({"ratio" if a.config == "lpnet" else "result": out}, a.dump_outputs)
     host_issue_ms = host_s[0] / a.steps * 1e3
     dt_nosg = None
     if sg:                                                             # beside it: the same K steps without the collectives
@@ -970,6 +1008,8 @@ def main():
         if dt_nosg is not None:
             line["without_collectives"] = {"value": imgs / dt_nosg, "ms_per_step": dt_nosg / a.steps * 1e3,
                                            "note": "the same K steps with every rank's shard already resident (no scatter / gather)"}
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
         if a.dry_run:
             line["dry_run"] = True
         os.write(json_fd, (json.dumps(line) + "\n").encode())

@@ -228,6 +228,25 @@ def test_bench_rccl_path_on_one_gpu(A):
     assert line["value"] > 0 and "without_collectives" in line
 
 
+def test_bench_dump_outputs_are_the_forward(A, tmp_path):
+    """bench.py --dump-outputs: the file holds the last timed graph replay's result, which equals an eager LPNet -> FDN forward of
+    the same seeded input with the same weights bit for bit."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from fdn_hip.pipeline import forward_streams
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2",
+                        "--height", "64", "--width", "96", "--no-cpu-baseline", "--no-roofline", "--dump-outputs", str(tmp_path)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["dumped_outputs"]["arrays"] == {"result": {"shape": [2, 3, 64, 96], "dtype": "float32"}}
+    net, lp = bench.build_models(torch.device("cuda:0"))
+    out = forward_streams(net, lp, bench.make_input(2, 64, 96, torch.device("cuda:0"), seed=1000))
+    assert np.array_equal(np.load(tmp_path / "result.npy"), out.cpu().numpy())
+
+
 def test_graphed_forward_bit_identical(A):
     """pipeline.GraphedForward (hipGraph capture + replay of the whole LPNet -> FDN forward) returns exactly the eager result:
     a shape met once runs eagerly, the second call captures, later calls replay with new input contents; a weight update, a

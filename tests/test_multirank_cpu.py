@@ -90,6 +90,47 @@ def test_bench_rejects_world_size_mismatch():
     assert r.returncode != 0 and "must agree" in (r.stderr + r.stdout)
 
 
+def test_bench_dump_outputs_dry_run(tmp_path):
+    """--dump-outputs writes what the timed path returned in its last step: the rank's own output on one rank, the gathered global batch
+    on the root of two; the inputs are the seeded ones, so the files are the stand-in forward (2 x + 1) of exactly those inputs."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
+    for n in (1, 2):
+        d = tmp_path / f"gpus{n}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--dry-run",
+                            "--batch", "3", "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["dumped_outputs"]["arrays"] == {"result": {"shape": [3 * n, 3, 16, 24], "dtype": "float32"}}
+        x = torch.cat([torch.rand(3, 3, 16, 24, generator=torch.Generator().manual_seed(1000 + k)) for k in range(n)])
+        got = np.load(d / "result.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, (x * 2.0 + 1.0).numpy())
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--dry-run"], env=env, capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_dump_outputs_fixed_sample_within_the_limit(tmp_path):
+    """An output above its share of the limit is stored as the same seeded sample of positions every time; float64 stays float64,
+    every other dtype becomes float32; the files together never exceed the limit."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    t = torch.rand(2, 3, 40, 50, generator=torch.Generator().manual_seed(4))
+    small = torch.rand(7, dtype=torch.float64, generator=torch.Generator().manual_seed(5))
+    limit = 4 * 4096
+    rec = bench.dump_outputs({"big": t.to(torch.bfloat16), "small": small}, str(tmp_path / "a"), limit=limit)
+    bench.dump_outputs({"big": t.to(torch.bfloat16), "small": small}, str(tmp_path / "b"), limit=limit)
+    assert rec["small"] == {"shape": [7], "dtype": "float64"} and rec["big"]["shape"] == [2, 3, 40, 50] and rec["big"]["dtype"] == "float32"
+    k = rec["big"]["sample"]["elements"]
+    assert 0 < k < t.numel()
+    big, big2 = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    pos = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(bench.DUMP_SAMPLE_SEED))[:k].sort().values
+    assert big.dtype == np.float32 and np.array_equal(big, big2) and np.array_equal(big, t.to(torch.bfloat16).float().reshape(-1)[pos].numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), small.numpy())
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= limit
+
+
 def test_bench_launcher_world_8_with_affinity():
     """The configs[3] launch shape on the CPU: 8 ranks, each pinned to its own cut of the host cores before any GPU call, the
     scatter / gather of a global batch of 8 x B through the timed loop (gloo)."""

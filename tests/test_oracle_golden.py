@@ -288,7 +288,15 @@ def test_edge_fdffn_fcaffn_and_dark_e2e():
     taps = {}
     with torch.no_grad():
         y = O.fcaffn(fx["x"], fx["amp"], fx["pha"], fx["img"], {"." + k: v for k, v in sd.items()}, "", taps)
-    EC.assert_channels_close(taps["xi"], fx["xi"], "fcaffn_edge.xi", 1e-5)
+    # channel 4, the pure cosine, is left with nothing but fp32 roundoff (its live bin has zero amplitude guidance): the rounding of the
+    # CPU's FFT library moves it by ~15 % of its own 5e-6 scale, and a CPU whose library rounds differently from the one that made the
+    # fixture lands ~25 % away.  It is judged against the float64 oracle (conditioning-aware); every other channel at its own scale
+    keep = [c for c in range(32) if c != 4]
+    EC.assert_channels_close(taps["xi"][:, keep], fx["xi"][:, keep], "fcaffn_edge.xi", 1e-5)
+    t64 = {}
+    with torch.no_grad():
+        O.fcaffn(*(fx[k].double() for k in ("x", "amp", "pha", "img")), {"." + k: v.double() for k, v in sd.items()}, "", t64)
+    assert_close_cond(taps["xi"][:, 4:5], fx["xi"][:, 4:5], t64["xi"][:, 4:5], "fcaffn_edge.xi[4]")
     assert rel_rms(y, fx["y"]) < 1e-5
     fx = fixture("fdn_tamed_64_dark")
     with torch.no_grad():

@@ -1,5 +1,5 @@
 import ctypes, os, statistics, sys
-sys.path.insert(0, "/root/repo/fdn-tip2025_amd")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "fdn-tip2025_amd"))
 import torch, fdn_hip
 dev = torch.device("cuda:0")
 B, E, H, W = 8, 153, 184, 320

@@ -1,5 +1,5 @@
 import os, sys
-ROOT = "/root/repo" if os.path.isdir("/root/repo/tests") else os.getcwd()
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in ("fdn-tip2025_amd", "tests", "oracle"):
     sys.path.insert(0, os.path.join(ROOT, p))
 import numpy as np, torch

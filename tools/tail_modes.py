@@ -1,5 +1,5 @@
 import os, sys
-sys.path.insert(0, "/root/repo/fdn-tip2025_amd")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "fdn-tip2025_amd"))
 import torch
 from fdn_hip import ops
 dev = torch.device("cuda:0")
