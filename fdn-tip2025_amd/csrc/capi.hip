@@ -2,7 +2,7 @@
 #include "common.hpp"
 
 #include <atomic>
-extern "C" int fdn_abi_version(void) { return 15; }
+extern "C" int fdn_abi_version(void) { return 16; }
 
 // Diagnostic switch: 1 = every matrix product of the path on the fp32 MFMA (the round-2 kernels) instead of the split-bf16 forms on
 // v_mfma_f32_32x32x16_bf16, so that the cross-stream finding can be bisected.  Process-wide, default 0.
@@ -43,6 +43,7 @@ extern "C" const char* fdn_error_string(int code) {
 namespace {
 std::mutex g_mu;
 int g_cus_by_dev[64];                                             // 0 = not queried yet
+int g_cu_budget_by_dev[64];                                       // fdn_set_cu_budget: 0 = none (the device's own count)
 std::map<std::pair<const void*, int>, size_t> g_lds_limit;         // (kernel, device) -> dynamic LDS bytes already allowed
 struct OccKey {
     const void* k; int dev, threads; size_t lds;
@@ -71,16 +72,34 @@ bool fdn_occupancy(int* blocks_per_cu, const void* kernel, int threads, size_t l
     return true;
 }
 
-int fdn_device_cus() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-    std::lock_guard<std::mutex> lk(g_mu);
+namespace {
+int device_cus_locked(int dev) {                                  // g_mu held
     if (g_cus_by_dev[dev] == 0) {
         int n = 0;
         if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return -1;
         g_cus_by_dev[dev] = n;
     }
     return g_cus_by_dev[dev];
+}
+}  // namespace
+
+int fdn_device_cus() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (g_cu_budget_by_dev[dev] > 0) return g_cu_budget_by_dev[dev];
+    return device_cus_locked(dev);
+}
+
+extern "C" int fdn_set_cu_budget(int cus) {
+    if (cus < 0) return FDN_ERR_ARG;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return FDN_ERR_ARG;
+    std::lock_guard<std::mutex> lk(g_mu);
+    const int n = device_cus_locked(dev);
+    if (n <= 0 || cus > n) return FDN_ERR_ARG;                    // never more workgroups than the device holds
+    g_cu_budget_by_dev[dev] = cus;
+    return FDN_OK;
 }
 
 bool fdn_allow_dynamic_lds(const void* kernel, size_t bytes) {

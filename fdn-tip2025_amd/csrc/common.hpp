@@ -19,7 +19,7 @@ static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // Launch-time device facts, cached per device ordinal (a process may drive several GPUs from several threads; plain
 // function-local statics would freeze the first device's answer).  fdn_device_cus: compute units of the CURRENT device
-// (<= 0 on error).  fdn_allow_dynamic_lds: raise a kernel's dynamic-LDS limit once per (kernel, device).
+// (<= 0 on error), or the budget fdn_set_cu_budget set for it - every persistent grid and channel-group choice reads this.  fdn_allow_dynamic_lds: raise a kernel's dynamic-LDS limit once per (kernel, device).
 int fdn_device_cus();
 bool fdn_allow_dynamic_lds(const void* kernel, size_t bytes);
 bool fdn_matrix_pipe_f32();                                   // fdn_set_matrix_pipe(1): no bf16-MFMA kernel is launched

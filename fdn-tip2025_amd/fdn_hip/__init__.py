@@ -37,7 +37,7 @@ class FdnHipError(RuntimeError):
     pass
 
 
-ABI_VERSION = 15         # include/fdn_hip.h: bumped on any signature change
+ABI_VERSION = 16         # include/fdn_hip.h: bumped on any signature change
 
 
 def lib_path():
@@ -121,6 +121,27 @@ def matrix_pipe():
 def matrix_pipe_mode():
     """the name last given to set_matrix_pipe (part of the capture key of pipeline.GraphedForward / GraphedStep)"""
     return _matrix_pipe
+
+
+_cu_budgets = {}         # device index -> the budget last set there (0 = the device's own count: not kept)
+
+
+def set_cu_budget(n):
+    """Launch geometry of the current device as if it had `n` compute units (fdn_set_cu_budget, ABI 16): the persistent kernels
+    then walk more tiles per workgroup and the patch-FFT kernels take wider channel groups.  A test and partitioning aid; results do
+    not change.  0 restores the device's count; n < 0 or above it raises."""
+    n = int(n)
+    check(lib().fdn_set_cu_budget(n), "fdn_set_cu_budget")
+    d = torch.cuda.current_device()
+    if n:
+        _cu_budgets[d] = n
+    else:
+        _cu_budgets.pop(d, None)
+
+
+def cu_budget():
+    """the budget set on the current device, 0 = none (part of the capture key of pipeline.GraphedForward / GraphedStep)"""
+    return _cu_budgets.get(torch.cuda.current_device(), 0)
 
 
 def bf16_mfma_launches():

@@ -50,6 +50,13 @@ int fdn_set_matrix_pipe(int mode);
 /* ABI 11: number of bf16-MFMA kernel launches this process has enqueued so far (every launcher counts; what mode 1 promises is that
  * this number stands still).  Diagnostic; no reference counterpart. */
 long fdn_bf16_mfma_launches(void);
+/* ABI 16: compute-unit budget of the CURRENT device, a test and partitioning aid (no reference counterpart).  Every launch geometry the
+ * library derives from the CU count - the persistent grids of fdn_conv1x1, the fp32-MFMA 3x3 conv, fdn_fcaffn_in, fdn_fdsa_out and
+ * fdn_ffn_tail (form 0), the channels per workgroup of fdn_fdffn_mid and fdn_fdsa_core - uses `cus` instead of the device's count, so a
+ * small budget runs many tiles per workgroup and large channel groups.  Results do not depend on it (no reduction is split across
+ * workgroups).  0 restores the device's count; a value below 0 or above the device's count returns FDN_ERR_ARG (a grid larger than the
+ * device holds is never made).  Default 0. */
+int fdn_set_cu_budget(int cus);
 
 /* ------------------------------------------------------------------------------------------
  * 1x1 convolution as fp32-MFMA GEMM with fused prologue / epilogue.

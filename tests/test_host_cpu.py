@@ -57,6 +57,15 @@ def test_argument_validation_without_gpu(lib):
     assert lib.fdn_fdsa_tail_pack_floats(48, 57, 48, 129) == 0                      # no project_in behind the C = 48 tail
     ring = lib.fdn_fdsa_scratch_floats(8, 38, 736, 1280)
     assert ring == lib.fdn_fdsa_scratch_floats(1, 38, 64, 64) == 16384 + 4096 * 4 * 38 * 256      # a ring: independent of the image
+    # (ABI 16) the CU budget: below 0 or above the device's count is refused (without a device every non-zero budget is above it),
+    # and the Python wrapper keeps no record of a refused one
+    import fdn_hip
+    assert lib.fdn_set_cu_budget(-1) == 1 and lib.fdn_set_cu_budget(1 << 20) == 1
+    before = dict(fdn_hip._cu_budgets)
+    for n in (-1, 1 << 20):
+        with pytest.raises(fdn_hip.FdnHipError):
+            fdn_hip.set_cu_budget(n)
+    assert fdn_hip._cu_budgets == before
 
 
 def test_state_dict_layout_matches_reference():
@@ -345,6 +354,21 @@ def test_graph_key_covers_every_routing_switch():
             assert pipeline.weights_signature(m) != base, f"ops.{name} is not part of the graph key"
         finally:
             setattr(ops, name, old)
+    assert pipeline.weights_signature(m) == base
+    # (ABI 16) the CU budget decides the launch geometry of the persistent and channel-grouped kernels: a graph captured under one budget must
+    # not replay under another (set directly: fdn_hip.set_cu_budget needs a device)
+    import fdn_hip
+    saved = dict(fdn_hip._cu_budgets)
+    keys = set()
+    try:
+        for budgets in ({}, {0: 1}, {0: 7}, {1: 1}):
+            fdn_hip._cu_budgets.clear()
+            fdn_hip._cu_budgets.update(budgets)
+            keys.add(pipeline.weights_signature(m))
+    finally:
+        fdn_hip._cu_budgets.clear()
+        fdn_hip._cu_budgets.update(saved)
+    assert len(keys) == 4, "fdn_hip.set_cu_budget is not part of the graph key"
     assert pipeline.weights_signature(m) == base
     with torch.no_grad():
         m.weight.add_(1.0)                      # an in-place weight update is seen too
