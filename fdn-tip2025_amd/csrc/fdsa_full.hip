@@ -101,10 +101,7 @@ struct FullGeo {
 };
 
 template <int C, int PT, bool LN>
-#ifndef FDN_FULL_WGS
-#define FDN_FULL_WGS 0          // 0: the geometry's choice
-#endif
-__global__ __launch_bounds__(256, (FDN_FULL_WGS ? FDN_FULL_WGS : FullGeo<C, PT>::WGS)) void fdsa_full_kernel(FullArgs a) {
+__global__ __launch_bounds__(256, (FullGeo<C, PT>::WGS)) void fdsa_full_kernel(FullArgs a) {
     typedef FullGeo<C, PT> G;
     constexpr int CHW = G::CHW, CE = G::CE, MTH = G::MTH, TWP = G::TWP, NPX = G::NPX, HW_ = G::HW_, HP = G::HP, NS = G::NS, NSW = G::NSW;
     constexpr int FRS = G::FRS, FPL = G::FPL, KST = G::KST, KS = G::KS, NCH = G::NCH, NMT = G::NMT, NOS = G::NOS, SKS = G::SKS, VPS = G::VPS;
@@ -217,10 +214,7 @@ __global__ __launch_bounds__(256, (FDN_FULL_WGS ? FDN_FULL_WGS : FullGeo<C, PT>:
     stage_store(0);                      // (visible behind the first barrier)
     // the to_hidden operands of the NEXT chunk are requested behind the inverse rows, so that P0 does not start with an L2 round trip
     // (8-channel chunks: all 7 fragments, 28 registers; at 16-channel chunks the 26 fragments do not fit: read on the fly)
-#ifndef FDN_FULL_AWA
-#define FDN_FULL_AWA -1
-#endif
-    constexpr int AWN = FDN_FULL_AWA >= 0 ? FDN_FULL_AWA : (MTH == 1 ? KS : 0);      // fragments held ahead (0: none)
+    constexpr int AWN = MTH == 1 ? KS : 0;      // fragments held ahead (0: none)
     fdn_u32x4 aw[AWN > 0 ? AWN : 1];
     auto aw_fetch = [&](int ch) {
         const fdn_u32x4* wp = a.wth + ((long)(ch * MTH) * KS) * 64 + lane;

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(NW * 64, SH <= 19 ? 2 : 1) void fdsa_out_kernel(FoA
             const unsigned vo = (4u * kh * P + pix) * 4u;
             float sm = 0.f;
             // the residual operand is requested as one batch before the stores: interleaved with them every load is
-            // waited for on its own (16 memory round trips per tile instead of one; tools/gemm_trace.py)
+            // waited for on its own (16 memory round trips per tile instead of one; measured with s_memtime stamps)
             float rres[MT * 16];
 #pragma unroll
             for (int i = 0; i < MT * 16; ++i)

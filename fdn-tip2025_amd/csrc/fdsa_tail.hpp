@@ -68,11 +68,6 @@ __device__ __forceinline__ void tl_ring_release(const TailIo& io) {
 
 // Level-1 form (E <= 2 SH <= 38, N <= 32): a lane owns two horizontally adjacent pixels (8-byte lanes), a wave two tile rows; fp32 MFMA.
 // Mirrors fdsa_out_vec_kernel<19, 1, true, false, 2, 4, false>.
-#ifdef FDN_FUSED_TRACE
-#define TLTR(i) if (trc) trc[40 + (i)] = __builtin_amdgcn_s_memtime();       // (tools/fused_trace.py --tail: the tail's stamps sit behind five chunks' worth)
-#else
-#define TLTR(i)
-#endif
 // PIN (round 6): the FDFFN that follows every FDSA starts with project_in(LayerNorm(y)) (FDN_arch.py:456, :673) - per pixel, on exactly the values and
 // statistics this epilogue holds in registers.  It runs here as gemm_split_strip_kernel<2, FDN_PRO_LN> does (fdn_conv1x1's kernel for this shape: the
 // normalised values cut into three bf16 parts, six products per 16-deep k-step on v_mfma_f32_32x32x16_bf16, bias in the accumulator, same k slots, same
@@ -81,7 +76,7 @@ __device__ __forceinline__ void tl_ring_release(const TailIo& io) {
 // lds_pin: [NT tiles][2 k-steps][3 parts][64 lanes] 16-byte A operands of the LayerNorm-folded weights, then NT * 32 bias floats.
 // FULL: E == 2 SH and N == 32 (the stock level 1: E = 38, C = 32) - no channel-range predicates (205 selects + 36 compares of the 1,350 vector instructions)
 template <int SH, bool PIN = false, int NT = 3, bool FULL = false>
-__device__ __forceinline__ void fdsa_tail_px2(const TailIo& io, const float* lds, const float* lds_pin = nullptr, unsigned long long* trc = nullptr) {
+__device__ __forceinline__ void fdsa_tail_px2(const TailIo& io, const float* lds, const float* lds_pin = nullptr) {
     typedef fdn_f32x2 T;
     typedef float f32x16 __attribute__((ext_vector_type(16)));
     constexpr int E2 = 2 * SH, WS = 33;
@@ -143,7 +138,6 @@ __device__ __forceinline__ void fdsa_tail_px2(const TailIo& io, const float* lds
             const int e = 2 * s + kh;
             cur[s] = ((cur[s] - m) * rs * tg[g * E2 + e] + tb[g * E2 + e]) * vv[s];      // norm_g(out_g) * v_value  :633-638
         }
-        if (g == 0) { TLTR(3) }
         if (g == 2) {
             tl_ring_release(io);                 // (the last group's values are in registers: nothing of the block is read any more)
 #pragma unroll
@@ -158,8 +152,6 @@ __device__ __forceinline__ void fdsa_tail_px2(const TailIo& io, const float* lds
             acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa, cur[s].x, acc[0], 0, 0, 0);
             acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa, cur[s].y, acc[1], 0, 0, 0);
         }
-        if (g == 0) { TLTR(4) }
-        if (g == 2) { TLTR(5) }
     }
     // ---- epilogue: residual, store, next LayerNorm's statistics (fdsa_out_vec_kernel's) -------------------------------------
     T outv[16];
@@ -189,7 +181,6 @@ __device__ __forceinline__ void fdsa_tail_px2(const TailIo& io, const float* lds
             __builtin_amdgcn_raw_buffer_store_b64(fdn_u32x2{__float_as_uint(rstd.x), __float_as_uint(rstd.y)}, rs_, vs, P4, 0);
         }
         if constexpr (PIN) {
-            TLTR(6)
             fdn_u32x4 Bf[2][2][3];                                   // [pixel of the pair][k-step][part]
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
@@ -250,7 +241,6 @@ __device__ __forceinline__ void fdsa_tail_px2(const TailIo& io, const float* lds
             }
         }
     }
-    if constexpr (PIN) { TLTR(7) } else { TLTR(6) }
 }
 
 // Level-2 form (E <= 2 SH <= 76, N <= 64): one pixel per lane, a wave takes its two tile rows one after the other; project_out on the bf16 matrix pipe
@@ -267,8 +257,7 @@ typedef __attribute__((address_space(3))) const fdn_u32x4* lds_cu4;
 // PIN (C = 64 only): the following FDFFN's project_in (64 -> Hd <= 32 NT) as gemm_split_strip_kernel<4, FDN_PRO_LN> computes it - see fdsa_tail_px2; its
 // packed operands ([NT][4 k-steps][3 parts][64 lanes] x 16 bytes, then 32 NT bias floats) are read from the image in global memory (72 KB: L1 / L2 hits)
 template <int SH, int MT, bool FULL = false, bool PIN = false, int NT = 6>          // FULL: E == 2 SH and N == 32 MT (the stock level 2: E = 76, C = 64): no channel-range predicates
-__device__ FDN_TAIL_FN void fdsa_tail_px1(const TailIo& io, lds_cf tg, lds_cf tb, lds_cu4 W0, lds_cu4 W1, const float* gimg,
-                                              unsigned long long* trc = nullptr) {
+__device__ FDN_TAIL_FN void fdsa_tail_px1(const TailIo& io, lds_cf tg, lds_cf tb, lds_cu4 W0, lds_cu4 W1, const float* gimg) {
     typedef float f32x16 __attribute__((ext_vector_type(16)));
     constexpr int E2 = 2 * SH, NQ = (SH + 7) / 8;
     const int E = io.E, N = io.N;
@@ -341,7 +330,6 @@ __device__ FDN_TAIL_FN void fdsa_tail_px1(const TailIo& io, lds_cf tg, lds_cf tb
                 const int e = 2 * s + kh;
                 cur[s] = ((cur[s] - m) * rs * tg[g * E2 + e] + tb[g * E2 + e]) * vv[s];      // norm_g(out_g) * v_value  :633-638
             }
-            if (g == 0 && rnd == 0) { TLTR(3) }
             if (g == 2 && rnd == 0) {          // the second row's v_value and group 0: v_value was last used just above, the idle set held group 1
                 const unsigned voff1 = voff_of(1);
 #pragma unroll
@@ -376,14 +364,12 @@ __device__ FDN_TAIL_FN void fdsa_tail_px1(const TailIo& io, lds_cf tg, lds_cf tb
                 }
             }
             if (g == 0 && rnd == 0) {
-                TLTR(4)
                 // group 1's operands were requested (LDS-DMA into the spectra's array) by all four waves behind the barrier in front of this function:
                 // every wave's share has to have landed before any wave reads them
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
             }
         }
-        if (rnd == 0) { TLTR(5) }
         // ---- epilogue: residual (one batch), store, next LayerNorm's statistics (fdsa_out_vec_kernel's) ----
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
@@ -478,7 +464,6 @@ __device__ FDN_TAIL_FN void fdsa_tail_px1(const TailIo& io, lds_cf tg, lds_cf tb
             }
         }
     }
-    TLTR(6)
 }
 __host__ __device__ constexpr int tl_pin_floats_l2(int NT) { return NT * 4 * 3 * 64 * 4 + 256; }     // level 2: four k-steps
 __host__ __device__ constexpr int tl_pin_floats(int NT) { return NT * 2 * 3 * 64 * 4 + 256; }        // A operands + one KB of bias

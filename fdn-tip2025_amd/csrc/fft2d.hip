@@ -866,17 +866,11 @@ template <int R, int P> struct ColPlan {
     static constexpr size_t lds = ((size_t)R * KS + (size_t)(P - 1) * R) * sizeof(float2);
 };
 
-#ifndef FDN_COLS_NB3
-#define FDN_COLS_NB3 16
-#endif
-#ifndef FDN_COLS_WGS3
-#define FDN_COLS_WGS3 1
-#endif
 template <int R, int P, int MODE>
 // (three workgroups per CU where the LDS allows it, R <= 23.  Round 3 ran the FCAFFN mode at two: inlined 32 times, its full-range sincos
 //  redo took 256 registers, and capped at 168 the hot path spilled - 0.99 against 0.78 ms.  Round 4: the redo is a rolled loop over the
 //  thread's LDS cells and the guidance records come in batches of 2 instead of 8: 168 registers, no scratch, 9.34 -> 8.22 ms per step)
-__global__ __launch_bounds__((ColPlan<R, P>::NT), (FDN_COLS_WGS3 && 3 * ColPlan<R, P>::lds <= 160 * 1024) ? 3 : 2) void fft_cols_rp_kernel(ColArgs a, const float2* __restrict__ twT) {
+__global__ __launch_bounds__((ColPlan<R, P>::NT), (3 * ColPlan<R, P>::lds <= 160 * 1024) ? 3 : 2) void fft_cols_rp_kernel(ColArgs a, const float2* __restrict__ twT) {
     constexpr int H = R * P, TC = 256 / P, CJ = 32 / P, NG = 8, KS = ColPlan<R, P>::KS, NJ = R * NG, NT = ColPlan<R, P>::NT;
     static_assert(TC / CJ == NG, "8 column groups");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_cols[];
@@ -932,7 +926,7 @@ __global__ __launch_bounds__((ColPlan<R, P>::NT), (FDN_COLS_WGS3 && 3 * ColPlan<
     const unsigned kstep = (unsigned)(R * Wf);      // bins between k2 and k2 + 1
     // guidance records in batches, one batch in flight ahead of the arithmetic: 8 per batch (96 registers for the two buffers) with two
     // workgroups per CU, 4 per batch (48) where the LDS leaves room for a third workgroup
-    constexpr int NB = (FDN_COLS_WGS3 && 3 * ColPlan<R, P>::lds <= 160 * 1024) ? FDN_COLS_NB3 : 4, BS = 32 / NB;
+    constexpr int NB = (3 * ColPlan<R, P>::lds <= 160 * 1024) ? 16 : 4, BS = 32 / NB;
     fdn_u32x4 g0[2][BS];
     fdn_u32x2 g1[2][BS];
     __amdgpu_buffer_rsrc_t rg = rz;

@@ -32,7 +32,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // The activation / epilogue kind are wave-uniform runtime values of the descriptor.  Tested per element they cost a chain
 // of scalar compare-and-branch per output value (the switch of apply_act alone is ~8 branches: 5.3k of a 23.5k-cycle output
-// tile of the level-3 to_hidden conv went there, tools/gemm_trace2.py).  Each kernel therefore writes its epilogue once as a
+// tile of the level-3 to_hidden conv went there, measured with s_memtime stamps).  Each kernel therefore writes its epilogue once as a
 // generic lambda over two integral constants and picks the copy once per tile.
 template <int V> using IC = std::integral_constant<int, V>;
 #define FDN_EPI_MODES(act_c, epi_c)                                                                     \
@@ -200,15 +200,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && !EARLY) ? ((MT <= 2 && PRO == 
             x_issue(cur, 0, xa, ya);
         }
         int step = 0;
-#ifdef FDN_GEMM_TRACE   // tools/gemm_trace.py: per-step s_memtime stamps of waves 0 and 4 of workgroup 0 into d.mul (vec4 = 12345)
-        unsigned long long* trc = (d.vec4 == 12345 && blockIdx.x == 0 && (wave == 0 || wave == 4) && lane == 0)
-                                      ? reinterpret_cast<unsigned long long*>(const_cast<float*>(d.mul)) + (wave ? 1024 : 0) : nullptr;
-#define TRC(i) if (trc && step < 120) trc[step * 8 + (i)] = __builtin_amdgcn_s_memtime();
-#else
-#define TRC(i)
-#endif
         while (live) {
-            TRC(0)
             // next step
             int ntile = tile, nc = c + 1;
             if (nc == nch) { nc = 0; ntile = tile + gridDim.x; }
@@ -244,7 +236,6 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && !EARLY) ? ((MT <= 2 && PRO == 
                 }
             }
 
-            TRC(1)
             // ---- compute step (tile, c) -----------------------------------------------------------
             const float* Wc = Wl + (g.resident ? c : (step & 1)) * CH;
 #pragma unroll
@@ -268,7 +259,6 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && !EARLY) ? ((MT <= 2 && PRO == 
                     acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(wrow[m * 32], bv, acc[m], 0, 0, 0);
             }
 
-            TRC(2)
             // ---- epilogue at the last chunk of a tile --------------------------------------------------
             if (c == nch - 1) {
                 if (cur.ok) {
@@ -281,7 +271,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && !EARLY) ? ((MT <= 2 && PRO == 
                     // the residual / mul / add operands of one 32-channel tile are requested as a batch before its
                     // stores: interleaved with the stores hipcc waits for every load separately (it cannot prove res
                     // and out distinct) - 64 memory round trips per tile at MT = 4, 92k of a tile's 228k cycles
-                    // (tools/gemm_trace.py)
+                    // (measured with s_memtime stamps)
                     // batch size by register budget: MT = 1 lives on 128 registers (2 workgroups per CU); the wide LN3_GATE
                     // kernels sit at 256 already and keep the one-by-one form
                     // (this kernel keeps the runtime tests of d.act / d.epi per element: resolved per tile as in the other kernels, the
@@ -366,13 +356,10 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && !EARLY) ? ((MT <= 2 && PRO == 
                     for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
             }
 
-            TRC(3)
             if (!g.resident) {
                 if (nlive) w_stash((step + 1) & 1);
-                TRC(4)
                 __syncthreads();
             }
-            TRC(5)
             // advance
             if (nlive && nc == 0) { cur = nxt; stats_load(cur); }
 #pragma unroll
@@ -973,15 +960,7 @@ __global__ __launch_bounds__(512) void conv1x1_smallk_stream_vec_kernel(fdn_conv
         stats_issue(cur);
     }
     int wstep = 0;
-#ifdef FDN_GEMM_TRACE   // tools/gemm_trace2.py: s_memtime stamps per output tile (waves 0 and 4 of workgroup 0) into d.mul (vec4 = 12345)
-    unsigned long long* trc2 = (d.vec4 == 12345 && blockIdx.x == 0 && (wave == 0 || wave == 4) && lane == 0)
-                                   ? reinterpret_cast<unsigned long long*>(const_cast<float*>(d.mul)) + (wave ? 1024 : 0) : nullptr;
-#define TR2(i) if (trc2 && wstep < 120) trc2[wstep * 8 + (i)] = __builtin_amdgcn_s_memtime();
-#else
-#define TR2(i)
-#endif
     while (live) {
-        TR2(6)
         if (PRO != FDN_PRO_NONE) {
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
@@ -1001,7 +980,6 @@ __global__ __launch_bounds__(512) void conv1x1_smallk_stream_vec_kernel(fdn_conv
             const int mnext = (m + 1 < ntiles) ? m + 1 : 0;
             const bool more = (m + 1 < ntiles) || nlive;
             const bool refill = nlive && m == ntiles - 1;
-            TR2(0)
             if (more) w_fetch(mnext);                              // next weight tile: L2 -> registers
             f32x16 acc[VEC];
 #pragma unroll
@@ -1030,7 +1008,6 @@ __global__ __launch_bounds__(512) void conv1x1_smallk_stream_vec_kernel(fdn_conv
                     for (int i = 0; i < 8; ++i) xa[grp * 8 + i] = bloadv<VEC>(rn, voffn, (unsigned)(2 * (grp * 8 + i)) * P4);
                 }
             }
-            TR2(1)
             auto epilogue = [&](auto act_c, auto epi_c) __attribute__((always_inline)) {
                 FDN_EPI_MODES(act_c, epi_c)
                 (void)epi_;
@@ -1047,11 +1024,8 @@ __global__ __launch_bounds__(512) void conv1x1_smallk_stream_vec_kernel(fdn_conv
             }
             };
             FDN_ACT_DISPATCH(epilogue);
-            TR2(2)
             if (more) w_stash((wstep + 1) & 1);
-            TR2(3)
             __syncthreads();
-            TR2(4)
         }
         cur = nxt; tile = ntile; live = nlive;
     }
@@ -1476,9 +1450,7 @@ extern "C" int fdn_conv1x1(const fdn_conv1x1_desc* dp, fdn_stream_t stream) {
     if (d.epi == FDN_EPI_RES) FDN_CHECK_ARG(d.res);
     if (d.epi == FDN_EPI_MULADD) FDN_CHECK_ARG(d.mul && d.add);
     if (d.stats_out) FDN_CHECK_ARG(d.N <= 160);
-#ifndef FDN_GEMM_TRACE
     d.vec4 = 0;
-#endif
     // 32-bit buffer offsets: every per-image plane set must stay below 4 GiB (incl. the padded K / N tails)
     {
         const unsigned long long lim = 0xFFFFFFFFull, P4 = 4ull * d.P;

@@ -688,10 +688,7 @@ int launch_strip(const fdn_conv1x1_desc& d, hipStream_t s) {
     a.tiles_per_img = cdiv(d.P, TP);
     a.total_ptiles = d.B * a.tiles_per_img;
     a.ntiles = 1;
-#ifndef FDN_STRIP2
-#define FDN_STRIP2 1
-#endif
-    if constexpr (FDN_STRIP2 && (3 * NKS * 2 * 32) % 256 == 0 && NKS >= 6) {
+    if constexpr ((3 * NKS * 2 * 32) % 256 == 0 && NKS >= 6) {
         const long wbytes = (long)cdiv(d.N, TN) * ((d.K + KC - 1) / KC) * BLK * 16;      // = fdn_conv1x1_pack_bytes(N, K, 0)
         if (wbytes < 0x7FFFFFFFL) {
             fdn_note_bf16_launch();

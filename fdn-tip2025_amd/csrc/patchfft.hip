@@ -11,9 +11,6 @@
 #include "patch_fft.hpp"
 #include "fdsa_tail.hpp"
 #include <type_traits>
-#ifndef FDN_RD_VOTE
-#define FDN_RD_VOTE 1      // replace_denormals by wave vote (fdsa_bin, patch_fft.hpp); 0: every compare / select as written (A/B builds)
-#endif
 
 namespace {
 
@@ -218,11 +215,7 @@ __global__ __launch_bounds__(256, 3) void fdsa_core_kernel(const float* __restri
             }
             return m;
         };
-#if FDN_RD_VOTE
         if (__builtin_amdgcn_ballot_w64(column(std::false_type{}) < 1e-10f) != 0) column(std::true_type{});
-#else
-        column(std::true_type{});
-#endif
         fft8<true>(o1);
         fft8<true>(o2);
         fft8<true>(o3);
@@ -276,25 +269,8 @@ constexpr int CPB_MIN = 4, CPB_MAX = 22;
 constexpr int HALO2 = (TH + 4) * (TW + 4);
 constexpr int HPT2 = (HALO2 + 255) / 256;               // 10 elements per thread
 
-// (round 6) tools/tail_trace.py mid: -DFDN_MID_TRACE - per wave, summed over its channels, the s_memtime clocks of phase A (ring conv + GELU + forward
-// rows), barrier, B (park the next halo + columns), barrier, C (inverse rows + second conv + stores), barrier; -DFDN_KOM_GELU / _CONV2 / _COLS / _STORE /
-// _LOADS knock a piece out (results are wrong: timing only)
-#ifdef FDN_MID_TRACE
-constexpr int MT_NWG = 512;
-__device__ unsigned long long g_mid_trace[MT_NWG * 4 * 16];
-#define MTR(var) const unsigned long long var = __builtin_amdgcn_s_memtime();
-#else
-#define MTR(var)
-#endif
 template <bool V4, bool IBF, bool OBF>      // IBF / OBF: x / out are stored as bf16 (fp32 math either way; V4 needs fp32 input)
-#ifndef FDN_MID_WGS
-#define FDN_MID_WGS 3
-#endif
-#ifndef FDN_MID_CONV2_LATE
-#define FDN_MID_CONV2_LATE 1
-#endif
-
-__global__ __launch_bounds__(256, FDN_MID_WGS) void fdffn_mid_kernel(const float* __restrict__ x, const float* __restrict__ w0,
+__global__ __launch_bounds__(256, 3) void fdffn_mid_kernel(const float* __restrict__ x, const float* __restrict__ w0,
                                                            const float* __restrict__ w2, const float* __restrict__ ffta,
                                                            const float* __restrict__ fftp, float* __restrict__ out, int Hd,
                                                            int H, int W, int tiles_x, int ntiles, int CPB) {
@@ -302,11 +278,6 @@ __global__ __launch_bounds__(256, FDN_MID_WGS) void fdffn_mid_kernel(const float
     __shared__ float mid[(TH + 2) * LSM];           // gelu(dw0(x)) on halo 1
     __shared__ __attribute__((aligned(16))) float2 S[NP * PS];
     __shared__ float2 filt[40];                     // ffta * e^{-i fftp} per (ky, kx)
-#ifdef FDN_MID_TRACE
-    const unsigned long long mt_entry = __builtin_amdgcn_s_memtime();
-    unsigned long long mt_sum[6] = {0, 0, 0, 0, 0, 0};
-    int mt_nch = 0;
-#endif
 
     const int tid = threadIdx.x;
     const int ngroups = (Hd + CPB - 1) / CPB;
@@ -361,13 +332,10 @@ __global__ __launch_bounds__(256, FDN_MID_WGS) void fdffn_mid_kernel(const float
     // (round 6) The loop issues the SAME loads on every path: a channel that does not exist is requested through a descriptor of zero records (returns 0,
     // moves nothing).  With the request inside `if (more)` the compiler's wait-count pass merged the two paths to "nothing younger in flight": the top of
     // every channel waited for one of the two stores just issued (vmcnt(1) in front of the halo request) and wave 0, which builds the filter, for both
-    // (vmcnt(0)) - the kernel ran 19 % faster without its stores (tools/tail_trace.py, profiles/r06_tail_mid_trace.txt).
+    // (vmcnt(0)) - the kernel ran 19 % faster without its stores (profiles/r06_tail_mid_trace.txt).
     const rsrc_t rdead = mk_rsrc(x, 0u);
     const rsrc_t rfa = mk_rsrc(ffta, (unsigned)Hd * 160u), rfp = mk_rsrc(fftp, (unsigned)Hd * 160u);
     auto fetch = [&](int c, bool live) {
-#ifdef FDN_KOM_LOADS
-        live = live && c == cbase;
-#endif
         const rsrc_t ri = live ? rin : rdead;
         // (the plane offset must reach the loads in a scalar register: the compiler keeps the strength-reduced c * hw4 of the channel loop in a
         //  VECTOR register and then wraps every load in a waterfall loop - 12 per channel, tools/isa_waterfall.py)
@@ -416,7 +384,6 @@ __global__ __launch_bounds__(256, FDN_MID_WGS) void fdffn_mid_kernel(const float
         const int c = cbase + ci;
         if (c >= Hd) break;                                   // uniform
         const bool more = ci + 1 < CPB && c + 1 < Hd;
-        MTR(mt0)
         {
             fetch(c + 1, more);                               // next channel's halo flies during this one's math
             const rsrc_t ra = more ? rfa : rdead, rp = more ? rfp : rdead;
@@ -448,21 +415,15 @@ __global__ __launch_bounds__(256, FDN_MID_WGS) void fdffn_mid_kernel(const float
 #pragma unroll
                     for (int dx = 0; dx < 3; ++dx) o8[j] = fmaf(k0[dy * 3 + dx], v[j + dx], o8[j]);
             }
-#ifndef FDN_GELU_SCALAR
             if (ring_inside) {                                    // uniform: the whole ring of this tile lies in the image (all but border tiles)
 #pragma unroll
                 for (int j = 0; j < 8; j += 2) {                  // GELU on pairs: packed fp32 for the polynomial and the products
-#ifdef FDN_KOM_GELU
-                    const fdn_f32x2 gv = fdn_f32x2{o8[j], o8[j + 1]};
-#else
                     const fdn_f32x2 gv = gelu_fast2(fdn_f32x2{o8[j], o8[j + 1]});
-#endif
                     mid[r * LSM + c0 + j] = gv.x;
                     mid[r * LSM + c0 + j + 1] = gv.y;
                 }
                 return;
             }
-#endif
             const int y = ty0 - 1 + r;
             const bool yok = y >= 0 && y < H;
 #pragma unroll
@@ -507,19 +468,13 @@ __global__ __launch_bounds__(256, FDN_MID_WGS) void fdffn_mid_kernel(const float
 #pragma unroll
             for (int kx = 0; kx < 5; ++kx) S[patch * PS + kx * KXS + rr] = o[kx];
         }
-        MTR(mt1)
         __syncthreads();
-        MTR(mt2)
 
         // ---- B: tin is free: park the prefetched halo; second conv; column transforms --------------
         stash();                                                  // (behind the last channel: zeros, read by nobody)
         auto second_conv = [&](float (&sp)[8]) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) sp[j] = 0.f;
-#ifdef FDN_KOM_CONV2
-            sp[0] = mid[(py * 8 + rr) * LSM + px * 8];
-            return;
-#endif
 #pragma unroll
             for (int dy = 0; dy < 3; ++dy) {
                 float v[10];
@@ -531,22 +486,13 @@ __global__ __launch_bounds__(256, FDN_MID_WGS) void fdffn_mid_kernel(const float
                     for (int dx = 0; dx < 3; ++dx) sp[j] = fmaf(k2[dy * 3 + dx], v[j + dx], sp[j]);
             }
         };
-#if FDN_MID_CONV2_LATE == 0
-        float sp[8];
-        second_conv(sp);
-#endif
         // columns: forward, z * ffta * e^{-i fftp}, inverse  (FDN_arch.py:460-469)
-#ifdef FDN_KOM_COLS
-        if (false) {
-#else
         if (tid < NP * 5) {
-#endif
             const int pj = tid / 5, kx = tid - pj * 5;
             float2 z[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) z[i] = S[pj * PS + kx * KXS + i];
             fft8<false>(z);
-#if FDN_RD_VOTE
             // replace_denormals (:460) touches a value only when |v| < 1e-10 - in practice the imaginary parts of the four self-conjugate bins
             // (exactly 0 for kx = 0, 4 at ky = 0, 4) and nothing else.  Those two are replaced as written; for the other 14 values the wave takes
             // the minimum magnitude and runs the compare / select pairs only when some lane needs one (same result bit for bit; 32 -> 13
@@ -569,19 +515,12 @@ __global__ __launch_bounds__(256, FDN_MID_WGS) void fdffn_mid_kernel(const float
                 const float2 a = z[ky], b = filt[ky * 5 + kx];
                 z[ky] = make_float2(fmaf(a.x, b.x, -(a.y * b.y)), fmaf(a.x, b.y, a.y * b.x));
             }
-#else
-#pragma unroll
-            for (int ky = 0; ky < 8; ++ky)
-                z[ky] = cmul(make_float2(rd1(z[ky].x), rd1(z[ky].y)), filt[ky * 5 + kx]);     // :461-468
-#endif
             fft8<true>(z);
             constexpr float sc = 1.0f / 64.0f;
 #pragma unroll
             for (int i = 0; i < 8; ++i) S[pj * PS + kx * KXS + i] = make_float2(z[i].x * sc, z[i].y * sc);
         }
-        MTR(mt3)
         __syncthreads();
-        MTR(mt4)
 
         // ---- C: inverse rows + spatial branch, 32-byte segments to global --------------------------------
         if (more) build_filter();                                 // the columns of this channel are done with `filt`; (fa, fp) of channel c + 1 landed long ago
@@ -591,39 +530,14 @@ __global__ __launch_bounds__(256, FDN_MID_WGS) void fdffn_mid_kernel(const float
             for (int kx = 0; kx < 5; ++kx) xk[kx] = S[patch * PS + kx * KXS + rr];
             float r[8];
             irfft8_row(xk, r);
-#if FDN_MID_CONV2_LATE
             float sp[8];
             second_conv(sp);
-#endif
 #pragma unroll
             for (int j = 0; j < 8; ++j) r[j] += sp[j];                                                              // :470
-#ifdef FDN_KOM_STORE
-            if (r[0] == 123.456f)
-#endif
             st_store8<OBF>(r, rout, ooff, (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)c * hwo)));
         }
-        MTR(mt5)
         __syncthreads();                                          // S, mid, filt are rewritten by the next channel
-#ifdef FDN_MID_TRACE
-        {
-            const unsigned long long mt6 = __builtin_amdgcn_s_memtime();
-            mt_sum[0] += mt1 - mt0; mt_sum[1] += mt2 - mt1; mt_sum[2] += mt3 - mt2; mt_sum[3] += mt4 - mt3; mt_sum[4] += mt5 - mt4; mt_sum[5] += mt6 - mt5;
-            ++mt_nch;
-        }
-#endif
     }
-#ifdef FDN_MID_TRACE
-    {
-        const unsigned rel = blockIdx.x - gridDim.x / 2;
-        if (rel < (unsigned)MT_NWG && (tid & 63) == 0) {
-            unsigned long long* t = g_mid_trace + ((long)rel * 4 + (tid >> 6)) * 16;
-            const unsigned long long now = __builtin_amdgcn_s_memtime();
-#pragma unroll
-            for (int i = 0; i < 6; ++i) t[i] = mt_sum[i];
-            t[6] = (unsigned long long)mt_nch; t[7] = now - mt_entry;
-        }
-    }
-#endif
 }
 
 
@@ -675,10 +589,8 @@ struct FusedArgs {
     float* h;            // TAIL 3: the following FDFFN's project_in output [B][Hd][H][W] (h_bf16: stored as bf16)
     int Hd, h_bf16;
 };
-#ifndef FDN_RING
-#define FDN_RING 1          // TAIL kernels: 1 = `out` is a RING of per-(CU, resident workgroup) blocks behind FDN_RING_SLOTS flag words (0 = free); 0 = one block per tile (A/B builds)
-#endif
-// (round 6) The tile-local hand-off as a ring.  With one block per TILE (4.6 GB per launch at level 1) every byte of it is written to HBM once; a
+// (round 6) TAIL kernels: `out` is a RING of per-(CU, resident workgroup) blocks behind FDN_RING_SLOTS flag words (0 = free), the tile-local hand-off.
+// With one block per TILE (4.6 GB per launch at level 1) every byte of it is written to HBM once; a
 // workgroup only needs its block for its own lifetime, so the blocks are handed out per RESIDENT workgroup instead - CU (XCC_ID, SE_ID, SH_ID, CU_ID of
 // HW_ID) x the two workgroups a CU holds (80 KB of LDS each) - and rewritten in place: ~80 MB that stay in the 256 MB Infinity Cache (tools/micro/ring_probe.hip).
 // A slot is taken with two atomic exchanges in flight at once (one round trip; the loser of a race retries) and given back by the wave whose last
@@ -687,34 +599,17 @@ constexpr int FDN_RING_CUS = 2048;                 // 3 + 3 + 1 + 4 id bits
 constexpr int FDN_RING_SLOTS = 2 * FDN_RING_CUS;
 constexpr int FDN_RING_HDR = 16384;                // floats in front of the blocks (the flags, padded to 64 KB)
 
-#ifndef FDN_FUSED_WGS
-#define FDN_FUSED_WGS 2
-#endif
-#ifndef FDN_STAGE_OPAQUE
-#define FDN_STAGE_OPAQUE 1      // 1: the tail + project_in kernels (TAIL 3) rebuild stage_fetch's indices per chunk (as C = 64 does) instead of carrying them: carried they
-                                // are spilled there (a scratch reload per chunk behind vmcnt(0)): 3.575 -> 3.525 ms at C = 32, 0.755 -> 0.736 at C = 24 (profiles/r06_tail_ab6*.txt)
-#endif
-#ifndef FDN_FUSED_CELLS
-#define FDN_FUSED_CELLS 1
-#endif
-#ifdef FDN_FUSED_TRACE      // tools/fused_trace.py: s_memtime stamps of every wave of FT_NWG workgroups from the middle of the grid (phase timeline per SIMD)
-constexpr int FT_NWG = 512;
-__device__ unsigned long long g_fused_trace[FT_NWG * 4 * 64];
-#define FTR(i) if (trc && ch < 7) trc[ch * 8 + (i)] = __builtin_amdgcn_s_memtime();
-#else
-#define FTR(i)
-#endif
 // TAIL (round 6): 0 = the (out1|out2|out3|v_value) planes go to the [B][4E][H][W] tensor for fdn_fdsa_out; 1 = they go to this tile's own 4E x 1 KB
 // block of a scratch tensor and the workgroup runs fdn_fdsa_out's arithmetic on them itself (fdsa_tail.hpp): the whole sub-block in one launch
 template <int C, bool LN, bool OBF, int TAIL = 0>          // OBF: the (out1|out2|out3|v_value) planes are stored as bf16
-__global__ __launch_bounds__(256, FDN_FUSED_WGS) void fdsa_fused_kernel(FusedArgs a) {
+__global__ __launch_bounds__(256, 2) void fdsa_fused_kernel(FusedArgs a) {
     static_assert(!TAIL || !OBF, "the in-kernel tail reads fp32 planes");
     // (round 4) C <= 32: the hidden tile is ONE plane per channel of (q, k, v, v_value) CELLS - the MFMA rows of a chunk are channel-major,
     // so a lane's accumulator holds whole cells - and the taps are (wq, wk, wv, wvv) cells too: a window position is one 16-byte read
     // and the four depthwise convs advance as two v_pk_fma_f32 (144 packed FMAs per thread and chunk where the three row-phase stencils
     // took 216 scalar ones and wave 3 ran the fourth beside the column phase).  C >= 48 (108 / 144 registers of strips) keeps the planar form.
-    constexpr bool CELLS = FDN_FUSED_CELLS && (C + 15) / 16 <= 2;
-    __shared__ __attribute__((aligned(16))) float hid[32 * FPL + (FDN_FUSED_WGS == 1 ? 2048 : 0)];      // (A/B hook: a pad that leaves room for one workgroup per CU only)
+    constexpr bool CELLS = (C + 15) / 16 <= 2;
+    __shared__ __attribute__((aligned(16))) float hid[32 * FPL];
     __shared__ __attribute__((aligned(16))) float2 S[3 * NP * PS];
     __shared__ __attribute__((aligned(16))) float wks[32 * 9];        // depthwise taps of the chunk: [kind * 8 + channel][9]; CELLS: [channel][tap][kind]
     __shared__ __attribute__((aligned(16))) float fgs[FEG * 40];      // fft gains of the chunk's channels: [channel][ky][kx]
@@ -733,21 +628,8 @@ __global__ __launch_bounds__(256, FDN_FUSED_WGS) void fdsa_fused_kernel(FusedArg
     rsrc_t rout = TAIL ? mk_rsrc(scr_tile, 4u * E * 1024u)
                        : mk_rsrc(reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.out) + (long)b * 4 * E * P * OES), 4u * E * hwo);
 
-#ifdef FDN_FUSED_TRACE
-    unsigned long long* trc = nullptr;
-    {
-        const unsigned base = gridDim.x / 2, rel = blockIdx.x - base;
-        if (rel < (unsigned)FT_NWG && lane == 0) {
-            trc = g_fused_trace + ((long)rel * 4 + wave) * 64;
-            unsigned hwid, xcc;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-            trc[60] = hwid; trc[61] = xcc; trc[62] = blockIdx.x; trc[63] = __builtin_amdgcn_s_memtime();
-        }
-    }
-#endif
-    __shared__ int ring_s[4];                      // (TAIL, ring) [0] the workgroup's slot, [1] waves whose read-back has landed, [2..3] its block's address
-    if constexpr (TAIL != 0 && FDN_RING) {
+    __shared__ int ring_s[4];                      // (TAIL) [0] the workgroup's slot, [1] waves whose read-back has landed, [2..3] its block's address
+    if constexpr (TAIL != 0) {
         if (tid == 0) {
             unsigned hwid, xcc;
             asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
@@ -847,10 +729,11 @@ __global__ __launch_bounds__(256, FDN_FUSED_WGS) void fdsa_fused_kernel(FusedArg
         //  recomputed per chunk instead, ~30 vector instructions.  Together with the strips' LDS offsets (mfma_phase), wave 3's coordinates and the
         //  one-output-at-a-time recombination of the column phase: 19 -> 0 spilled registers, level 2 1.371 -> 1.327 ms, interleaved, bit-identical
         //  (profiles/r05_l_fused64_ab.txt).  The same treatment of stage_store's two addresses costs 10 %, and C <= 48 keeps the hoisted form:
-        //  this change alone cost the C = 32 kernel 2.7 %)
+        //  this change alone cost the C = 32 kernel 2.7 %.  The tail + project_in kernels (TAIL 3) take it too: carried, the indices are spilled
+        //  there (a scratch reload per chunk behind vmcnt(0)): 3.575 -> 3.525 ms at C = 32, 0.755 -> 0.736 at C = 24, profiles/r06_tail_ab6*.txt)
         const int tid_o = tid;
         const int tid = [&] {
-            if constexpr (KST >= 4 || (FDN_STAGE_OPAQUE && TAIL == 3)) { int t = threadIdx.x; asm volatile("" : "+v"(t)); return t; }
+            if constexpr (KST >= 4 || TAIL == 3) { int t = threadIdx.x; asm volatile("" : "+v"(t)); return t; }
             else return tid_o;
         }();
         auto tap_of = [&](int i) {                                      // element i < 288: row m = kind * 8 + channel, tap i % 9
@@ -937,13 +820,10 @@ __global__ __launch_bounds__(256, FDN_FUSED_WGS) void fdsa_fused_kernel(FusedArg
         const int e0 = ch * FEG;
         const int e = e0 + el;
         const bool more = ch + 1 < a.nchunks;                       // uniform
-        FTR(0)
         mfma_phase(ch);
         if (more) stage_fetch(ch + 1);
-        FTR(1)
         __syncthreads();
-        FTR(2)
-        if constexpr (TAIL != 0 && FDN_RING) {
+        if constexpr (TAIL != 0) {
             // the slot (taken by thread 0 at entry: its round trip ran under the strip loads) is visible behind the first barrier.  Rebuilt per chunk
             // from the LDS word instead of carried through the loop: a loop-carried descriptor cost the chunk loop three spilled registers
             scr_tile = reinterpret_cast<const float*>(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(ring_s[3]) << 32) |
@@ -1015,9 +895,7 @@ __global__ __launch_bounds__(256, FDN_FUSED_WGS) void fdsa_fused_kernel(FusedArg
                 for (int kx = 0; kx < 5; ++kx) S[(t * NP + slot) * PS + kx * KXS + row] = sp[kx];
             }
         }
-        FTR(3)
         __syncthreads();
-        FTR(4)
 
         // ---- columns: thread = (slot, kx): forward, recombine, inverse (as fdsa_core_kernel) ------------------------
         if (tid < NP * 5) {
@@ -1057,13 +935,9 @@ __global__ __launch_bounds__(256, FDN_FUSED_WGS) void fdsa_fused_kernel(FusedArg
                 }
                 return m;
             };
-#if FDN_RD_VOTE
             // (C = 64 stays as written: the second evaluation path costs 14 spilled registers there, 1.36 -> 1.42 ms)
             if constexpr (KST >= 4) column(std::true_type{});
             else if (__builtin_amdgcn_ballot_w64(column(std::false_type{}) < 1e-10f) != 0) column(std::true_type{});
-#else
-            column(std::true_type{});
-#endif
             if constexpr (KST >= 4) {
 #pragma unroll
                 for (int t = 0; t < 3; ++t) {
@@ -1110,9 +984,7 @@ __global__ __launch_bounds__(256, FDN_FUSED_WGS) void fdsa_fused_kernel(FusedArg
                 st_store8<OBF>(o8, rout, ev < E ? opix + (unsigned)(3 * E + ev) * hwo : OOB, 0);
             }
         }
-        FTR(5)
         __syncthreads();
-        FTR(6)
 
         // ---- inverse rows, 32-byte segments straight to global (out1|out2|out3) --------------------------------------
 #pragma unroll
@@ -1124,7 +996,6 @@ __global__ __launch_bounds__(256, FDN_FUSED_WGS) void fdsa_fused_kernel(FusedArg
             irfft8_row(xk, r8);
             st_store8<OBF>(r8, rout, e < E ? opix + (unsigned)(t * E + e) * hwo : OOB, 0);
         }
-        FTR(7)
         if (more) stage_store();        // taps and gains of the next chunk (this chunk's were last read before the third barrier)
         // (measured: an explicit s_waitcnt vmcnt(0) here - what a scratch reload implies - costs 1.8 % at C = 32, 1 % at C = 64: profiles/r05_l_fused64_ab.txt)
         // (the next chunk's row phase rewrites S behind the barrier at the top of the loop, i.e. after every thread has finished these reads)
@@ -1137,9 +1008,6 @@ __global__ __launch_bounds__(256, FDN_FUSED_WGS) void fdsa_fused_kernel(FusedArg
         constexpr bool PIN = TAIL == 3;          // + the next sub-block's project_in (operands behind the tail's own image)
         constexpr int NBLK0 = tl_image_floats(SH, 1) / 256;
         constexpr int NBLK = NBLK0 + (PIN ? tl_pin_floats(3) / 256 : 0);
-#ifdef FDN_FUSED_TRACE
-        if (trc) trc[40] = __builtin_amdgcn_s_memtime();
-#endif
         const rsrc_t rtw = mk_rsrc(a.tw, (unsigned)NBLK * 1024u);
 #pragma unroll
         for (int i = 0; i < (NBLK + 3) / 4; ++i) {
@@ -1148,13 +1016,7 @@ __global__ __launch_bounds__(256, FDN_FUSED_WGS) void fdsa_fused_kernel(FusedArg
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rtw, (__attribute__((address_space(3))) void*)(hid + blk * 256), 16, (unsigned)(blk * 1024 + lane * 16), 0, 0, 0);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef FDN_FUSED_TRACE
-        if (trc) trc[41] = __builtin_amdgcn_s_memtime();
-#endif
         __syncthreads();
-#ifdef FDN_FUSED_TRACE
-        if (trc) trc[42] = __builtin_amdgcn_s_memtime();
-#endif
         TailIo io;
         io.scr = scr_tile;
         io.res = a.res ? a.res + (long)b * a.N * P : nullptr;
@@ -1164,15 +1026,11 @@ __global__ __launch_bounds__(256, FDN_FUSED_WGS) void fdsa_fused_kernel(FusedArg
         io.h = PIN ? reinterpret_cast<float*>(reinterpret_cast<char*>(a.h) + (long)b * a.Hd * P * (a.h_bf16 ? 2 : 4)) : nullptr;
         io.Hd = a.Hd;
         io.h_bf16 = a.h_bf16;
-        io.ring_flag = FDN_RING ? reinterpret_cast<unsigned*>(a.out) + ring_s[0] : nullptr;
+        io.ring_flag = reinterpret_cast<unsigned*>(a.out) + ring_s[0];
         io.ring_cnt = ring_s + 1;
         // (C = 32 is always the stock E = 38, N = 32: fdn_fdsa_fused_tail checks it; C = 24 keeps the channel-range predicates)
         constexpr bool FULL = C == 32;
-#ifdef FDN_FUSED_TRACE
-        fdsa_tail_px2<SH, PIN, 3, FULL>(io, hid, hid + NBLK0 * 256, trc);
-#else
         fdsa_tail_px2<SH, PIN, 3, FULL>(io, hid, hid + NBLK0 * 256);
-#endif
     }
     if constexpr (TAIL == 2 || TAIL == 4) {
         // ---- level 2 (fdsa_tail_px1): gamma -> wks, beta -> fgs, group 0's packed operands -> hid (all dead behind the last chunk's third barrier);
@@ -1187,20 +1045,11 @@ __global__ __launch_bounds__(256, FDN_FUSED_WGS) void fdsa_fused_kernel(FusedArg
                                                          (unsigned)((src_blk + blk) * 1024 + lane * 16), 0, 0, 0);
             }
         };
-#ifdef FDN_FUSED_TRACE
-        if (trc) trc[40] = __builtin_amdgcn_s_memtime();
-#endif
         dma(wks, 0, 1, 2);               // (waves 2 and 3 carry one block less of group 0's 30)
         dma(fgs, 1, 1, 3);
         dma(hid, 2, GB);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef FDN_FUSED_TRACE
-        if (trc) trc[41] = __builtin_amdgcn_s_memtime();
-#endif
         __syncthreads();
-#ifdef FDN_FUSED_TRACE
-        if (trc) trc[42] = __builtin_amdgcn_s_memtime();
-#endif
         dma(S, 2 + GB, GB);
         TailIo io;
         io.scr = scr_tile;
@@ -1211,13 +1060,9 @@ __global__ __launch_bounds__(256, FDN_FUSED_WGS) void fdsa_fused_kernel(FusedArg
         io.h = PIN2 ? a.h + (long)b * a.Hd * P : nullptr;
         io.Hd = a.Hd;
         io.h_bf16 = 0;
-        io.ring_flag = FDN_RING ? reinterpret_cast<unsigned*>(a.out) + ring_s[0] : nullptr;
+        io.ring_flag = reinterpret_cast<unsigned*>(a.out) + ring_s[0];
         io.ring_cnt = ring_s + 1;
-#ifdef FDN_FUSED_TRACE
-        fdsa_tail_px1<SH, MT, C == 64, PIN2>(io, (lds_cf)wks, (lds_cf)fgs, (lds_cu4)hid, (lds_cu4)S, a.tw, trc);
-#else
         fdsa_tail_px1<SH, MT, C == 64, PIN2>(io, (lds_cf)wks, (lds_cf)fgs, (lds_cu4)hid, (lds_cu4)S, a.tw);      // (C = 64 is always the stock E = 76: checked by the launcher)
-#endif
     }
 }
 
@@ -1295,19 +1140,13 @@ extern "C" int fdn_fdsa_core(const float* hidden, const float* dw_w, const float
     FDN_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 15) == 0);
     FDN_CHECK_ARG(16ull * E * H * W < 0x80000000ull);          // one image's 4E planes are addressed with 32-bit byte offsets
     const int tx = cdiv(W, TW), ty = cdiv(H, TH);
-#ifndef FDN_CORE_EPB
-#define FDN_CORE_EPB 0          // 0: chosen per launch
-#endif
-    int EPB = FDN_CORE_EPB;
-    if (EPB <= 0) {
-        const int cus = fdn_device_cus();
-        if (cus <= 0) return FDN_ERR_LAUNCH;
-        const long want = 8L * 3 * cus, per = (long)tx * ty * B;            // ~8 rounds of three workgroups per CU
-        long groups = (want + per - 1) / per;
-        groups = groups < 1 ? 1 : (groups > E ? E : groups);
-        EPB = (int)((E + groups - 1) / groups);
-        if (EPB > 8) EPB = 8;
-    }
+    const int cus = fdn_device_cus();
+    if (cus <= 0) return FDN_ERR_LAUNCH;
+    const long want = 8L * 3 * cus, per = (long)tx * ty * B;            // ~8 rounds of three workgroups per CU
+    long groups = (want + per - 1) / per;
+    groups = groups < 1 ? 1 : (groups > E ? E : groups);
+    int EPB = (int)((E + groups - 1) / groups);
+    if (EPB > 8) EPB = 8;
     const int ngrp = (E + EPB - 1) / EPB;
     if (W % 4 == 0 && (reinterpret_cast<uintptr_t>(hidden) & 15) == 0)
         hipLaunchKernelGGL(fdsa_core_kernel<true>, dim3((unsigned)(tx * ty) * ngrp * B), dim3(256), 0, static_cast<hipStream_t>(stream), hidden, dw_w,
@@ -1476,8 +1315,7 @@ extern "C" long fdn_fdsa_tail_pack_floats(int C, int E, int N, int Hd) {
 }
 extern "C" long fdn_fdsa_scratch_floats(int B, int E, int H, int W) {
     if (B <= 0 || E <= 0 || H <= 0 || W <= 0 || H % 8) return 0;
-    if (FDN_RING) return FDN_RING_HDR + (long)FDN_RING_SLOTS * 4 * E * 256;             // independent of the image: per resident workgroup
-    return (long)B * (H / FT_H) * cdiv(W, FT_W) * 4 * E * 256;
+    return FDN_RING_HDR + (long)FDN_RING_SLOTS * 4 * E * 256;             // independent of the image: per resident workgroup
 }
 extern "C" int fdn_fdsa_tail_pack(const float* w, const float* gamma3, const float* beta3, const float* pin_w, const float* pin_b, float* img, int C,
                                   int E, int N, int Hd, fdn_stream_t stream) {
@@ -1565,22 +1403,3 @@ extern "C" int fdn_fdsa_fused_tail(const float* x, long xbs, const float* stats,
     fdn_note_bf16_launch();
     return fdn_launch_status();
 }
-
-#ifdef FDN_MID_TRACE
-extern "C" int fdn_debug_mid_trace(void* host, long bytes, int clear) {          // trace builds only (tools/tail_trace.py); not part of the ABI
-    static unsigned long long z[MT_NWG * 4 * 16];
-    if (bytes > (long)sizeof(z)) return FDN_ERR_ARG;
-    if (clear) return hipMemcpyToSymbol(HIP_SYMBOL(g_mid_trace), z, sizeof(z), 0, hipMemcpyHostToDevice) == hipSuccess ? FDN_OK : FDN_ERR_LAUNCH;
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mid_trace), (size_t)bytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? FDN_OK : FDN_ERR_LAUNCH;
-}
-#endif
-#ifdef FDN_FUSED_TRACE
-extern "C" int fdn_debug_fused_trace(void* host, long bytes) {          // trace builds only (tools/fused_trace.py); not part of the ABI
-    if (bytes > (long)sizeof(unsigned long long) * FT_NWG * 4 * 64) return FDN_ERR_ARG;
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_fused_trace), (size_t)bytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? FDN_OK : FDN_ERR_LAUNCH;
-}
-extern "C" int fdn_debug_fused_trace_clear(void) {
-    static unsigned long long z[FT_NWG * 4 * 64];
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_fused_trace), z, sizeof(z), 0, hipMemcpyHostToDevice) == hipSuccess ? FDN_OK : FDN_ERR_LAUNCH;
-}
-#endif

@@ -219,6 +219,15 @@ def test_no_waterfall_loops_in_the_patch_kernels(tmp_path):
     assert {k: stats[k][0] for k in kernels if stats[k][0]} == {}
 
 
+def test_no_build_hooks_in_the_kernel_sources():
+    """The kernels compile in one form only: no `FDN_*` switch that an A/B build could flip with -D (build.sh defines none)."""
+    csrc = os.path.join(ROOT, "fdn-tip2025_amd", "csrc")
+    hook = re.compile(r"#\s*(ifdef|ifndef|if)\s+FDN_")
+    hits = [f"{name}:{i}: {line.strip()}" for name in sorted(os.listdir(csrc)) if name.endswith((".hip", ".hpp"))
+            for i, line in enumerate(open(os.path.join(csrc, name)), 1) if hook.search(line)]
+    assert hits == []
+
+
 def test_reference_driver_imports_through_the_shadow(tmp_path):
     """this package FIRST on PYTHONPATH, a reference checkout after it.  The checkout here is a stub laid out like the
     reference (basicsr/ WITHOUT an __init__.py, basicsr/utils/__init__.py with the four helpers, basicsr/models/__init__.py that must NOT run,

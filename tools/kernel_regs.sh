@@ -1,5 +1,5 @@
 #!/bin/bash
-# Registers / spills / LDS of every kernel of one csrc file:  tools/kernel_regs.sh <stem> [extra hipcc flags]   (e.g. fdsa_full -DFDN_FULL_AWA=0)
+# Registers / spills / LDS of every kernel of one csrc file:  tools/kernel_regs.sh <stem> [extra hipcc flags]   (e.g. patchfft -fslp-vectorize)
 stem=$1; shift
 d=$(mktemp -d)
 fl=""; case " patchfft ffn_tail fdsa_full " in *" $stem "*) fl="-fno-slp-vectorize";; esac
