@@ -23,7 +23,7 @@
 
 namespace {
 
-constexpr int MAX_STAGES = 16;
+constexpr int MAX_STAGES = FDN_FFT_MAX_STAGES;    // fdn_fft_route reports up to this many stages
 constexpr int NT = 256;
 
 struct Plan {
@@ -69,9 +69,12 @@ const float2* get_table(int N) {
     return d;
 }
 
-bool make_plan(int N, int tabN, Plan* p) {
+// the radix decomposition alone (host arithmetic, no table): what make_plan runs and what fdn_fft_route reports
+bool plan_radices(int N, Plan* p) {
     p->N = N;
     p->nst = 0;
+    p->tw = nullptr;
+    p->tab_mul = 0;
     int n = N;
     auto push = [&](int r) { if (p->nst < MAX_STAGES) p->radix[p->nst++] = r; };
     int n2 = n, odd[MAX_STAGES], nodd = 0;
@@ -84,7 +87,11 @@ bool make_plan(int N, int tabN, Plan* p) {
     while (n % 2 == 0) { push(2); n /= 2; }
     int prod = 1;
     for (int i = 0; i < p->nst; ++i) prod *= p->radix[i];
-    if (prod != N || tabN % N != 0) return false;
+    return prod == N;
+}
+
+bool make_plan(int N, int tabN, Plan* p) {
+    if (!plan_radices(N, p) || tabN % N != 0) return false;
     p->tw = get_table(tabN);
     p->tab_mul = tabN / N;
     return p->tw != nullptr;
@@ -111,6 +118,18 @@ bool is_prime(int n) {
     return true;
 }
 
+// radices with a register butterfly at every BIG >= 1 tier of fft_pass and a case in fft_run_inplace: the in-place column passes and
+// the Rader sub-transforms take only these
+bool reg_radix(int R) { return R == 2 || R == 3 || R == 4 || R == 5 || R == 7 || R == 17 || R == 23; }
+
+// Rader applies to p: a prime >= 29 whose p-1 factors into reg_radix radices (sub = that plan's radices, no table)
+bool rader_ok(int p, Plan* sub) {
+    if (p < 29 || !is_prime(p) || !plan_radices(p - 1, sub)) return false;
+    for (int i = 0; i < sub->nst; ++i)
+        if (!reg_radix(sub->radix[i])) return false;
+    return true;
+}
+
 // returns false when p is not prime / p-1 needs a radix without a register butterfly (caller keeps the gather pass)
 bool get_rader(int p, Rader* out) {
     int devid = 0;
@@ -122,13 +141,9 @@ bool get_rader(int p, Rader* out) {
     }
     Rader r = {};
     auto fail = [&]() { std::lock_guard<std::mutex> lk(g_mu); g_rader[{devid, p}] = Rader{}; return false; };
-    if (p < 29 || !is_prime(p)) return fail();
+    if (!rader_ok(p, &r.sub)) return fail();
     const int n = p - 1;
     if (!make_plan(n, n, &r.sub)) return fail();
-    for (int i = 0; i < r.sub.nst; ++i) {
-        const int R = r.sub.radix[i];
-        if (!(R == 2 || R == 3 || R == 4 || R == 5 || R == 7 || R == 17 || R == 23)) return fail();
-    }
     auto powmod = [&](long b, long e) { long x = 1; b %= p; while (e) { if (e & 1) x = x * b % p; b = b * b % p; e >>= 1; } return x; };
     int g = 0;
     for (int c = 2; c < p && !g; ++c) {
@@ -1133,30 +1148,38 @@ int launch_cols_rp(ColArgs a, long planes, fdn_stream_t stream) {
     return fdn_launch_status();
 }
 
-// the compile-time plans: H = 23 * {32, 16, 8} (720p pyramid), 17 * {32, 16, 8} (1080p levels 2, 3 and 544-row inputs)
+// the compile-time plans: H = 23 * {32, 16, 8} (720p pyramid), 17 * {32, 16, 8} (1080p levels 2, 3 and 544-row inputs), 34 * 32
+// (1088 rows: 1080p level 1), and the shapes the reference's own drivers feed: LOL-Blur frames 640 x 1120
+// (inference_fdn_lolblur.py:16-17, already x32) and LOL-v1 400 x 600 padded to 416 x 608 (inference_fdn_lolv1.py:52-64)
+bool cols_plan(int H, int* R, int* P) {
+    for (int r : {23, 17, 20, 13})
+        for (int p : {32, 16, 8})
+            if (H == r * p) { *R = r; *P = p; return true; }
+    if (H == 34 * 32) { *R = 34; *P = 32; return true; }
+    return false;
+}
+
 template <int MODE>
 int launch_cols_planned(const ColArgs& a, long planes, fdn_stream_t stream, bool* done) {
-    *done = true;
-    switch (a.H) {
-        case 23 * 32: return launch_cols_rp<23, 32, MODE>(a, planes, stream);
-        case 23 * 16: return launch_cols_rp<23, 16, MODE>(a, planes, stream);
-        case 23 * 8: return launch_cols_rp<23, 8, MODE>(a, planes, stream);
-        case 17 * 32: return launch_cols_rp<17, 32, MODE>(a, planes, stream);
-        case 17 * 16: return launch_cols_rp<17, 16, MODE>(a, planes, stream);
-        case 17 * 8: return launch_cols_rp<17, 8, MODE>(a, planes, stream);
-        case 34 * 32: return launch_cols_rp<34, 32, MODE>(a, planes, stream);       // 1088 rows: 1080p level 1
-        // the shapes the reference's own drivers feed: LOL-Blur frames 640 x 1120 (inference_fdn_lolblur.py:16-17, already x32) and
-        // LOL-v1 400 x 600 padded to 416 x 608 (inference_fdn_lolv1.py:52-64)
-        case 20 * 32: return launch_cols_rp<20, 32, MODE>(a, planes, stream);
-        case 20 * 16: return launch_cols_rp<20, 16, MODE>(a, planes, stream);
-        case 20 * 8: return launch_cols_rp<20, 8, MODE>(a, planes, stream);
-        case 13 * 32: return launch_cols_rp<13, 32, MODE>(a, planes, stream);
-        case 13 * 16: return launch_cols_rp<13, 16, MODE>(a, planes, stream);
-        case 13 * 8: return launch_cols_rp<13, 8, MODE>(a, planes, stream);
-        default: break;
+    int R = 0, P = 0;
+    *done = cols_plan(a.H, &R, &P);
+    if (!*done) return FDN_OK;
+    switch (R * 64 + P) {
+        case 23 * 64 + 32: return launch_cols_rp<23, 32, MODE>(a, planes, stream);
+        case 23 * 64 + 16: return launch_cols_rp<23, 16, MODE>(a, planes, stream);
+        case 23 * 64 + 8: return launch_cols_rp<23, 8, MODE>(a, planes, stream);
+        case 17 * 64 + 32: return launch_cols_rp<17, 32, MODE>(a, planes, stream);
+        case 17 * 64 + 16: return launch_cols_rp<17, 16, MODE>(a, planes, stream);
+        case 17 * 64 + 8: return launch_cols_rp<17, 8, MODE>(a, planes, stream);
+        case 34 * 64 + 32: return launch_cols_rp<34, 32, MODE>(a, planes, stream);
+        case 20 * 64 + 32: return launch_cols_rp<20, 32, MODE>(a, planes, stream);
+        case 20 * 64 + 16: return launch_cols_rp<20, 16, MODE>(a, planes, stream);
+        case 20 * 64 + 8: return launch_cols_rp<20, 8, MODE>(a, planes, stream);
+        case 13 * 64 + 32: return launch_cols_rp<13, 32, MODE>(a, planes, stream);
+        case 13 * 64 + 16: return launch_cols_rp<13, 16, MODE>(a, planes, stream);
+        case 13 * 64 + 8: return launch_cols_rp<13, 8, MODE>(a, planes, stream);
+        default: return FDN_ERR_UNSUPPORTED;                 // cols_plan lists a length this switch lacks
     }
-    *done = false;
-    return FDN_OK;
 }
 
 bool plan_big(const Plan& p) {
@@ -1198,12 +1221,63 @@ int inplace_tc(const Plan& p, int H) {
         bool ok = true;
         for (int i = 0; i < p.nst && ok; ++i) {
             const int R = p.radix[i];
-            if (!(R == 2 || R == 3 || R == 4 || R == 5 || R == 7 || R == 17 || R == 23)) ok = false;
+            if (!reg_radix(R)) ok = false;
             else if ((long)(H / R) * tc > (long)NT * (EMAX / R)) ok = false;
         }
         if (ok) return tc;
     }
     return 0;
+}
+
+// The route a generic (not compile-time planned) length takes, decided on the host from the length alone.  The launchers and
+// fdn_fft_route both read it, so the query cannot drift from what runs.
+constexpr size_t LDS_MAX = 160 * 1024;        // per workgroup (gfx950)
+
+struct Route {
+    int kind;                  // FDN_FFT_REFUSED / _PLANNED / _INPLACE / _PINGPONG / _RADER (include/fdn_hip.h)
+    int big;                   // BIG of the kernel instantiation
+    int width;                 // columns per workgroup (tc) / rows per workgroup (rpb)
+    Plan p;                    // radices only (no table)
+    Plan sub;                  // FDN_FFT_RADER: the length p-1 sub-plan
+    size_t lds;
+};
+
+// columns of length H: in-place passes if every radix has an in-place butterfly and fits, else ping-pong passes with pick_tc
+// columns per workgroup; refused when no tc fits or the buffers plus the twiddle table exceed the LDS of a workgroup
+void cols_route(int H, Route* r) {
+    *r = Route{};
+    if (!plan_radices(H, &r->p)) return;
+    const int itc = inplace_tc(r->p, H);
+    if (itc > 0) {
+        r->kind = FDN_FFT_INPLACE;
+        r->width = itc;
+        r->big = plan_big(r->p) ? 1 : 0;
+        r->lds = ((size_t)H * itc + H) * sizeof(float2);
+        return;
+    }
+    const int tc = pick_tc(H);
+    const size_t lds = (2UL * H * tc + H) * sizeof(float2);
+    if (tc == 0 || lds > LDS_MAX) return;
+    r->kind = FDN_FFT_PINGPONG;
+    r->width = tc;
+    r->big = plan_big2(r->p) ? 2 : plan_big(r->p) ? 1 : 0;
+    r->lds = lds;
+}
+
+// rows of width W (half-length M = W / 2) on the generic kernels: Stockham passes, or (forward only) Rader for a prime M;
+// refused when the ping-pong rows, the table and the Rader scratch exceed the LDS of a workgroup
+void rows_route(int W, bool fwd, Route* r) {
+    *r = Route{};
+    const int M = W / 2;
+    if (!plan_radices(M, &r->p)) return;
+    const bool rader = fwd && r->p.nst == 1 && rader_ok(M, &r->sub);   // prime half-length: convolution form instead of the O(N^2) gather
+    const int rpb = pick_rpb(M);
+    const size_t lds = (2UL * rpb * M + W + (rader ? (size_t)M + rpb : 0)) * sizeof(float2);
+    if (lds > LDS_MAX) return;
+    r->kind = rader ? FDN_FFT_RADER : FDN_FFT_PINGPONG;
+    r->width = rpb;
+    r->big = (plan_big(r->p) || (rader && plan_big(r->sub))) ? 1 : 0;
+    r->lds = lds;
 }
 
 template <int MODE, int BIG, bool INPL>
@@ -1225,23 +1299,17 @@ int launch_cols(ColArgs a, long planes, fdn_stream_t stream) {
         const int e = launch_cols_planned<MODE>(a, planes, stream, &done);
         if (done) return e;
     }
+    Route r;
+    cols_route(a.H, &r);
+    if (r.kind == FDN_FFT_REFUSED) return FDN_ERR_UNSUPPORTED;
     Plan p;
     if (!make_plan(a.H, a.H, &p)) return FDN_ERR_UNSUPPORTED;
-    const int itc = inplace_tc(p, a.H);
-    if (itc > 0) {
-        a.tc = itc;
-        a.tcs = __builtin_ctz(itc);
-        const size_t lds = ((size_t)a.H * a.tc + a.H) * sizeof(float2);
-        return plan_big(p) ? launch_cols_k<MODE, 1, true>(a, p, planes, lds, stream)
-                           : launch_cols_k<MODE, 0, true>(a, p, planes, lds, stream);
-    }
-    a.tc = pick_tc(a.H);
-    if (a.tc == 0) return FDN_ERR_UNSUPPORTED;
-    a.tcs = __builtin_ctz(a.tc);
-    const size_t lds = (2UL * a.H * a.tc + a.H) * sizeof(float2);
-    if (plan_big2(p)) return launch_cols_k<MODE, 2, false>(a, p, planes, lds, stream);
-    return plan_big(p) ? launch_cols_k<MODE, 1, false>(a, p, planes, lds, stream)
-                       : launch_cols_k<MODE, 0, false>(a, p, planes, lds, stream);
+    a.tc = r.width;
+    a.tcs = __builtin_ctz(r.width);
+    if (r.kind == FDN_FFT_INPLACE)
+        return r.big ? launch_cols_k<MODE, 1, true>(a, p, planes, r.lds, stream) : launch_cols_k<MODE, 0, true>(a, p, planes, r.lds, stream);
+    if (r.big == 2) return launch_cols_k<MODE, 2, false>(a, p, planes, r.lds, stream);
+    return r.big ? launch_cols_k<MODE, 1, false>(a, p, planes, r.lds, stream) : launch_cols_k<MODE, 0, false>(a, p, planes, r.lds, stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1579,15 +1647,49 @@ bool rows_plan(int W, int* R1, int* P) {
 
 extern "C" int fdn_fft_prepare(int n) {
     FDN_CHECK_ARG(n > 0);
-    for (int R : {23, 17, 20, 13})
-        for (int P : {32, 16, 8})
-            if (n == R * P && !get_table_rp(R, P)) return FDN_ERR_LAUNCH;      // column lengths with a compile-time plan
-    if (n == 34 * 32 && !get_table_rp(34, 32)) return FDN_ERR_LAUNCH;
+    {
+        int R = 0, P = 0;                                                       // column lengths with a compile-time plan
+        if (cols_plan(n, &R, &P) && !get_table_rp(R, P)) return FDN_ERR_LAUNCH;
+    }
     {
         int R1 = 0, P = 0;                                                      // row widths with a compile-time plan
         if (rows_plan(n, &R1, &P) && !get_table_rows_rp(R1, P)) return FDN_ERR_LAUNCH;
     }
     return get_table(n) ? FDN_OK : FDN_ERR_LAUNCH;
+}
+
+extern "C" int fdn_fft_route(int kind, int n, int* desc, int ndesc) {
+    FDN_CHECK_ARG(kind >= 0 && kind <= 2 && n >= 1 && desc && ndesc >= FDN_FFT_ROUTE_DESC);
+    FDN_CHECK_ARG(kind == 2 || n % 2 == 0);                                    // the row launchers take even widths only
+    for (int i = 0; i < FDN_FFT_ROUTE_DESC; ++i) desc[i] = 0;
+    int R = 0, P = 0;
+    if (kind == 2 ? cols_plan(n, &R, &P) : rows_plan(n, &R, &P)) {
+        desc[0] = FDN_FFT_PLANNED;
+        desc[2] = kind == 2 ? 256 / P : row_plan_groups(R, P) * (32 / P);    // columns / rows per workgroup
+        desc[4] = 2;
+        desc[5] = R;
+        desc[6] = P;
+        return FDN_OK;
+    }
+    Route r;
+    if (kind == 2) cols_route(n, &r);
+    else rows_route(n, kind == 0, &r);
+    desc[0] = r.kind;
+    if (r.kind == FDN_FFT_REFUSED) return FDN_OK;
+    desc[1] = r.big;
+    desc[2] = r.width;
+    const Plan& q = r.kind == FDN_FFT_RADER ? r.sub : r.p;
+    desc[3] = r.kind == FDN_FFT_RADER ? n / 2 : 0;
+    desc[4] = q.nst;
+    for (int i = 0; i < q.nst; ++i) {
+        const int x = q.radix[i];
+        // fft_pass: register butterflies for 2 / 4 / 3 / 5 / 7, + 17 / 23 at BIG >= 1, + 13 / 37 / 41 at BIG == 2; any other radix gathers
+        const bool reg = x == 2 || x == 4 || x == 3 || x == 5 || x == 7 || (r.big >= 1 && (x == 17 || x == 23)) ||
+                         (r.big == 2 && (x == 13 || x == 37 || x == 41));
+        desc[5 + i] = x;
+        desc[5 + MAX_STAGES + i] = (r.kind != FDN_FFT_INPLACE && !reg) ? 1 : 0;
+    }
+    return FDN_OK;
 }
 
 namespace {
@@ -1619,15 +1721,16 @@ extern "C" int fdn_rfft_rows(const float* in, float* out_c, long rows, int W, lo
 #undef FDN_CALL
         }
     }
+    Route r;
+    rows_route(W, true, &r);
+    if (r.kind == FDN_FFT_REFUSED) return FDN_ERR_UNSUPPORTED;
     Plan p;
     if (!make_plan(W / 2, W, &p)) return FDN_ERR_UNSUPPORTED;
     Rader rd = {};
-    const bool rader = p.nst == 1 && get_rader(W / 2, &rd);            // prime half-length: convolution form instead of the O(N^2) gather
-    if (!rader) rd = Rader{};
-    const int rpb = pick_rpb(W / 2);
-    const size_t lds = (2UL * rpb * (W / 2) + W + (rader ? (size_t)(W / 2) + rpb : 0)) * sizeof(float2);
-    if (lds > 160 * 1024) return FDN_ERR_UNSUPPORTED;
-    if (plan_big(p) || (rader && plan_big(rd.sub))) {
+    if (r.kind == FDN_FFT_RADER && !get_rader(W / 2, &rd)) return FDN_ERR_LAUNCH;
+    const int rpb = r.width;
+    const size_t lds = r.lds;
+    if (r.big) {
         if (int e = set_lds(rfft_rows_kernel<true>, lds)) return e;
         hipLaunchKernelGGL(rfft_rows_kernel<true>, dim3(cdiv(rows, rpb)), dim3(NT), lds, static_cast<hipStream_t>(stream), in,
                            reinterpret_cast<float2*>(out_c), W, rows, rpb, p, rd, pitch);
@@ -1668,13 +1771,15 @@ extern "C" int fdn_irfft_rows(const float* in_c, long in_row_bins, long in_plane
 #undef FDN_CALL
         }
     }
+    Route r;
+    rows_route(W, false, &r);
+    if (r.kind == FDN_FFT_REFUSED) return FDN_ERR_UNSUPPORTED;
     Plan p;
     if (!make_plan(W / 2, W, &p)) return FDN_ERR_UNSUPPORTED;
-    const int rpb = pick_rpb(W / 2);
-    const size_t lds = (2UL * rpb * (W / 2) + W) * sizeof(float2);
-    if (lds > 160 * 1024) return FDN_ERR_UNSUPPORTED;
+    const int rpb = r.width;
+    const size_t lds = r.lds;
     const long rows = planes * H;
-    if (plan_big(p)) {
+    if (r.big) {
         if (int e = set_lds(irfft_rows_kernel<true>, lds)) return e;
         hipLaunchKernelGGL(irfft_rows_kernel<true>, dim3(cdiv(rows, rpb)), dim3(NT), lds, static_cast<hipStream_t>(stream),
                            reinterpret_cast<const float2*>(in_c), in_row_bins, (long)H, in_plane_bins, out, W, H, rows, rpb,

@@ -492,6 +492,24 @@ def spec_pitch(Wf):
     return (Wf + 15) // 16 * 16
 
 
+FFT_ROUTES = ("refused", "planned", "inplace", "pingpong", "rader")      # FDN_FFT_* of include/fdn_hip.h, in order
+FFT_MAX_STAGES = 16                                                      # FDN_FFT_MAX_STAGES
+FFT_ROWS, FFT_IROWS, FFT_COLS = 0, 1, 2
+
+
+def fft_route(kind, n):
+    """The route the FFT launchers take for a length (fdn_fft_route; host arithmetic, no GPU needed).  kind: FFT_ROWS (fdn_rfft_rows of
+    width n, aligned input), FFT_IROWS (fdn_irfft_rows), FFT_COLS (the three column passes, length n).  Returns a dict: route (a name of
+    FFT_ROUTES), big, width (tc / rpb per workgroup), rader (prime half-length or 0), radices (of the Rader sub-transform for "rader",
+    the factors R, P for "planned") and gather (the radices that run the gather pass)."""
+    desc = (ctypes.c_int * (5 + 2 * FFT_MAX_STAGES))()
+    check(lib().fdn_fft_route(int(kind), int(n), desc, len(desc)), "fdn_fft_route")
+    nst = desc[4]
+    radices = tuple(desc[5 + i] for i in range(nst))
+    return {"route": FFT_ROUTES[desc[0]], "big": desc[1], "width": desc[2], "rader": desc[3], "radices": radices,
+            "gather": tuple(r for i, r in enumerate(radices) if desc[5 + FFT_MAX_STAGES + i])}
+
+
 def rfft_rows(x, pitch=None):
     """real [..., H, W] -> interleaved complex [..., H, pitch or W//2+1, 2] along the last axis (bins past W//2 are zeros)."""
     W = x.shape[-1]

@@ -36,7 +36,7 @@ enum { FDN_PRO_NONE = 0, FDN_PRO_LN = 1, FDN_PRO_LN3_GATE = 2, FDN_PRO_LN_MULADD
 enum { FDN_EPI_NONE = 0, FDN_EPI_RES = 1, FDN_EPI_MULADD = 2 };
 enum { FDN_RS_BILINEAR_HALF = 0, FDN_RS_BILINEAR_X2 = 1, FDN_RS_NEAREST_HALF = 2, FDN_RS_NEAREST_X2 = 3, FDN_RS_PIXEL_UNSHUFFLE = 4 };
 
-/* library version / build info: returns the ABI version (bumped on any signature change) */
+/* library version / build info: returns the ABI version (bumped on any signature change; 17 since fdn_fft_route) */
 int fdn_abi_version(void);
 const char* fdn_error_string(int code);
 /* Diagnostic switch, process-wide, default 0 = every matrix product that has a split-bf16 form runs on the bf16 matrix pipe
@@ -253,7 +253,8 @@ int fdn_img_mod_maps(const float* img, const float* w1_mul, const float* w3_mul,
 /* ------------------------------------------------------------------------------------------
  * Full-image real 2-D FFT pipeline, norm='backward' (torch.fft.rfft2 / irfft2 at FDN_arch.py:90,98,
  * :139,147, :411,418, :882-911).  Spectra are [planes][H][W/2+1] interleaved complex.
- * Any even W and any H are accepted (mixed radix; large primes use an O(N*R) gather pass).
+ * Any even W and any H that fit the LDS of a workgroup are accepted (mixed radix; large primes use an O(N*R) gather pass): H <= 4096,
+ * W <= 10240; fdn_fft_route says which route a length takes.
  * fdn_fft_prepare(n): build the immutable twiddle table of length n now (else first use does). */
 int fdn_fft_prepare(int n);
 /* sn[i] = sin(x[i]), cs[i] = cos(x[i]) with the library's own range reduction (what the polar <-> complex steps of the column
@@ -267,7 +268,7 @@ int fdn_sincos_f32(const float* x, float* sn, float* cs, long n, fdn_stream_t st
 int fdn_rfft_rows(const float* in, float* out_c, long rows, int W, long out_row_bins, fdn_stream_t stream);
 /* r2c along rows of the channel LayerNorm of x, normalised on load: x [B][C][H][W], stats [B][2][H*W] = (mean, rstd) of x over C,
  * gamma / beta [C] -> out_c [B*C*H][W/2+1] = rfft(norm(x)) (FDN_arch.py:675 + :411).  Widths with a compile-time plan only
- * (W = 2 * {20, 30} * {32, 16, 8}); else FDN_ERR_UNSUPPORTED: fdn_layernorm_chan + fdn_rfft_rows. */
+ * (W = 2 * {20, 30} * {32, 16, 8}, 2 * 19 * {16, 8}, 2 * 35 * {16, 8, 4}); else FDN_ERR_UNSUPPORTED: fdn_layernorm_chan + fdn_rfft_rows. */
 int fdn_rfft_rows_ln(const float* x, const float* stats, const float* gamma, const float* beta, float* out_c, int B, int C, int H,
                      int W, long out_row_bins, fdn_stream_t stream);
 /* c2r along rows: spectrum rows of `in_row_bins` bins (>= W/2+1; leading-slice crop of
@@ -290,6 +291,21 @@ int fdn_fft_cols_fcaffn(float* z, const float* guide, const float* wxa, const fl
  * self-conjugate bins of a real input (what a real-FFT library returns; keeps angle=+pi there). */
 int fdn_fft_cols_fwd(const float* z, float* out_abs, float* out_ang, long planes, int H, int Wf, int rd_before,
                      int fix_real, fdn_stream_t stream);
+/* ABI 17: the route the launchers above take for a length, decided on the host by the same code the launchers run; no HIP call, no
+ * table is built, so it answers on a host without a GPU.  kind: 0 = fdn_rfft_rows of width n, 1 = fdn_irfft_rows of width n (both: n even,
+ * else FDN_ERR_ARG), 2 = the column passes (fdn_fft_cols_fcaffn / _fwd / _inv_polar: one route for all three) of length n.  Rows are
+ * reported for 8-byte aligned pointers: at a planned width a misaligned input (fdn_rfft_rows) or output / residual (fdn_irfft_rows)
+ * takes the generic route instead.  desc[0 .. FDN_FFT_ROUTE_DESC) is filled with
+ *   [0] route: FDN_FFT_REFUSED (the launcher returns FDN_ERR_UNSUPPORTED), FDN_FFT_PLANNED (compile-time plan), FDN_FFT_INPLACE (columns:
+ *       in-place Stockham passes), FDN_FFT_PINGPONG (ping-pong Stockham passes), FDN_FFT_RADER (forward rows, prime half-length)
+ *   [1] BIG of the generic kernel (0, 1, or 2 for ping-pong columns)   [2] columns (tc) / rows (rpb) per workgroup
+ *   [3] the Rader prime (W/2), else 0   [4] nst, the number of stages: for Rader those of the length p-1 sub-transform, for a compile-time
+ *       plan the two factors R, P of n (columns) or W/2 (rows)
+ *   [5 + i] radix of stage i   [5 + FDN_FFT_MAX_STAGES + i] 1 if stage i runs the gather pass (no register butterfly at that BIG)
+ * kind outside 0..2, n < 1, desc NULL or ndesc < FDN_FFT_ROUTE_DESC: FDN_ERR_ARG. */
+enum { FDN_FFT_REFUSED = 0, FDN_FFT_PLANNED = 1, FDN_FFT_INPLACE = 2, FDN_FFT_PINGPONG = 3, FDN_FFT_RADER = 4 };
+enum { FDN_FFT_MAX_STAGES = 16, FDN_FFT_ROUTE_DESC = 5 + 2 * FDN_FFT_MAX_STAGES };
+int fdn_fft_route(int kind, int n, int* desc, int ndesc);
 /* mag,pha real planes [planes][Hin][Wfin] -> z = mag*e^{i pha} on the leading (H,Wf) slice ->
  * inverse column FFT -> z_out [planes][H][Wf] (FDN_arch.py:95-98, :144-147). */
 int fdn_fft_cols_inv_polar(const float* mag, const float* pha, int Hin, int Wfin, float* z_out, long planes, int H, int Wf,

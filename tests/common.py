@@ -83,3 +83,53 @@ def assert_close_cond(got, ref32, truth64, what, factor=4.0, floor=2e-6):
     assert e_got <= factor * e_ref + floor, f"{what}: rel-RMS err {e_got:.3e} > {factor}*{e_ref:.3e}+{floor}"
     assert p_got <= factor * p_ref + 10 * floor, f"{what}: p99.9 err {p_got:.3e} > {factor}*{p_ref:.3e}+{10*floor}"
     return e_got, e_ref
+
+
+
+def rd_replace(v):
+    """replace_denormals (FDN_arch.py:548-553): components in (-1e-10, 1e-10) become 1e-10"""
+    return torch.where((v < 1e-10) & (v > -1e-10), torch.full_like(v, 1e-10), v)
+
+
+def fcaffn_ref(z, amp, pha, wxa, wxp, dtype=torch.float64):
+    """Restatement of FDN_arch.py:411-418 for the column pass (forward FFT over H, modulation, unnormalised inverse) in `dtype`
+    (float64: the truth; float32: what torch.fft computes in the reference's precision); the phase is formed in float32 like the
+    kernel does, so that large phases compare bin for bin."""
+    Z = torch.fft.fft(torch.view_as_complex(z.to(dtype)), dim=2)
+    Zr = torch.complex(rd_replace(Z.real.float()).to(dtype), rd_replace(Z.imag.float()).to(dtype))
+    A = torch.einsum("ci,bihw->bchw", wxa.to(dtype), amp.to(dtype))
+    ph = torch.einsum("ci,bihw->bchw", wxp, pha).to(dtype) if wxp.abs().max() < 100 else (wxp[:, 0].view(1, -1, 1, 1) * pha[:, :1]).to(dtype)
+    out = Zr * A * torch.polar(torch.ones_like(ph), -ph)
+    return torch.view_as_real(torch.fft.ifft(out, dim=2) * Z.shape[2])
+
+
+# The route each length of the generic-FFT tests is chosen to exercise, as fdn_fft_route reports it (include/fdn_hip.h).  The CPU suite pins
+# these (a plan change that moves a length to another route fails there, not silently in a GPU test that no longer tests its route), and
+# tests/test_gpu_fft_generic.py runs each length against float64.
+# columns, length H: (route, BIG, tc, radices that run the gather pass)
+FFT_COL_ROUTES = {
+    18: ("inplace", 0, 32, ()), 98: ("inplace", 0, 32, ()), 120: ("inplace", 0, 32, ()),          # radix 3 / 7 / 5, tc 32
+    240: ("inplace", 0, 16, ()), 224: ("inplace", 0, 16, ()), 480: ("inplace", 0, 8, ()),          # tc 16 / 8 (224: radix 7)
+    112: ("inplace", 0, 32, ()),                                                                  # 224 x 352 frames, level 2
+    34: ("inplace", 1, 32, ()), 322: ("inplace", 1, 16, ()), 578: ("inplace", 1, 8, ()),          # 17 / 23 in place
+    690: ("inplace", 1, 8, ()),                                                                   # 23 * 5 * 3 * 2: at the job limit
+    66: ("pingpong", 0, 16, (11,)), 114: ("pingpong", 0, 16, (19,)), 194: ("pingpong", 0, 16, (97,)),
+    226: ("pingpong", 0, 8, (113,)), 242: ("pingpong", 0, 8, (11, 11)), 482: ("pingpong", 0, 8, (241,)),
+    816: ("pingpong", 1, 8, ()), 1104: ("pingpong", 1, 8, ()),                                    # 17 / 23 beside radices too wide to run in place
+    82: ("pingpong", 2, 16, ()), 296: ("pingpong", 2, 8, ()), 338: ("pingpong", 2, 8, ()), 546: ("pingpong", 2, 8, ()),   # 41 / 37 / 13
+    2178: ("pingpong", 0, 4, (11, 11)), 4094: ("pingpong", 1, 2, (89,)), 4096: ("pingpong", 0, 2, ()),                      # 4K frames
+    1: ("inplace", 0, 32, ()), 2: ("inplace", 0, 32, ()), 3: ("inplace", 0, 32, ()),
+    4097: ("refused", 0, 0, ()), 4480: ("refused", 0, 0, ()), 4482: ("refused", 0, 0, ()),    # ping-pong buffers + table > 160 KiB of LDS
+}
+# rows, width W: (forward route, BIG, rpb, radices that run the gather pass, Rader prime)
+FFT_ROW_ROUTES = {
+    160: ("pingpong", 0, 8, (), 0), 224: ("pingpong", 0, 8, (), 0), 352: ("pingpong", 0, 8, (11,), 0), 546: ("pingpong", 0, 7, (13,), 0),
+    176: ("pingpong", 0, 8, (11,), 0),                                                            # 224 x 352 frames, level 2
+    322: ("pingpong", 1, 8, (), 0), 544: ("pingpong", 1, 7, (), 0),                             # BIG rows (23, 17)
+    194: ("rader", 0, 8, (), 97), 226: ("rader", 0, 8, (), 113), 482: ("rader", 0, 8, (), 241), 1282: ("rader", 0, 3, (), 641),
+    274: ("rader", 1, 8, (), 137),                                                                # 136 = 17 * 4 * 2: a BIG sub-plan
+    26: ("pingpong", 0, 8, (13,), 0), 354: ("pingpong", 0, 8, (59,), 0), 178: ("pingpong", 0, 8, (89,), 0), 642: ("pingpong", 0, 6, (107,), 0),
+    2: ("pingpong", 0, 8, (), 0), 4: ("pingpong", 0, 8, (), 0), 6: ("pingpong", 0, 8, (), 0),
+    8192: ("pingpong", 0, 1, (), 0), 10240: ("pingpong", 0, 1, (), 0),
+    10242: ("refused", 0, 0, (), 0),
+}

@@ -11,7 +11,7 @@ import torch
 
 import edge_cases as EC
 import fdn_oracle as O
-from common import fdn_weights, fixture, fixture_weights, lpnet_weights, rel_rms
+from common import assert_close_cond, fdn_weights, fixture, fixture_weights, lpnet_weights, rel_rms
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -158,6 +158,49 @@ def test_fcaffn_at_bench_shapes_vs_oracle(A, name, c, H, W):
         got = m(dev(x), dev(amp), dev(pha), dev(img))
         ref = O.fcaffn(x, amp, pha, img, {"." + k: v for k, v in sd.items()}, "")
     assert _psnr_vs_oracle(got, ref) > 100.0, (name, H, W)
+
+
+@pytest.mark.parametrize("H,W", [(480, 544), (224, 352)])
+def test_generic_fft_blocks_at_product_frames_vs_oracle(A, H, W):
+    """Blocks whose full-image FFTs take the generic routes (tests/test_gpu_fft_generic.py runs each route at op level), at two frame sizes the
+    product pads to: 480 x 544 - in-place columns 480 / 240 / 120, BIG rows 544 / 272 / 136, fourier_fuse's 482 (gather 241) x 546 (gather 13)
+    and, at level 2, 242 (gather 11 x 11) x 274 (Rader with a radix-17 sub-plan); 224 x 352 - radix-7 in-place columns, gather-11 rows,
+    fourier_fuse's 226 (gather 113) x 354 (gather 59) and 114 (gather 19) x 178 (gather 89).  FCAFFN at every level, FreBlock at level 1,
+    fourier_fuse at levels 1 and 2, each against the fp32 oracle and its float64 restatement (conditioning-aware: fourier_fuse re-uses near-zero bins' phases)."""
+    torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))
+    P32 = lambda sd: {"." + k: v for k, v in sd.items()}
+    P64 = lambda sd: {"." + k: v.double() for k, v in sd.items()}
+    for lvl, (name, c) in enumerate((("fcaffn_c32_32x32", 32), ("fcaffn_c64_46x40", 64), ("fcaffn_c128_16x16", 128))):
+        h, w = H >> lvl, W >> lvl
+        sd = fixture_weights(name, fixture(name)["shapes"])
+        m = load(A.FCAFFN(c), sd)
+        g = torch.Generator().manual_seed(h + c)
+        x = torch.randn(1, c, h, w, generator=g)
+        amp = torch.rand(1, 3, h, w // 2 + 1, generator=g) * 30.0
+        pha = torch.rand(1, 3, h, w // 2 + 1, generator=g) * 6.2 - 3.1
+        img = torch.rand(1, 3, h, w, generator=g)
+        with torch.no_grad():
+            got = m(dev(x), dev(amp), dev(pha), dev(img))
+            ref = O.fcaffn(x, amp, pha, img, P32(sd), "")
+            t64 = O.fcaffn(x.double(), amp.double(), pha.double(), img.double(), P64(sd), "")
+        assert_close_cond(got, ref, t64, f"FCAFFN({c}) {h}x{w}")
+    sd_fb = fixture_weights("freblock_c12", fixture("freblock_c12")["shapes"])
+    fb = load(A.FreBlock(12), sd_fb)
+    sd_ff = fixture_weights("fourier_fuse_84_12", fixture("fourier_fuse_84_12")["shapes"])
+    ff = load(A.fourier_fuse(84, 12), sd_ff)
+    x = _rnd(1, 12, H, W, seed=H + 1)
+    with torch.no_grad():
+        got = fb(dev(x))
+        ref, t64 = O.freblock(x, P32(sd_fb), ""), O.freblock(x.double(), P64(sd_fb), "")
+    assert_close_cond(got, ref, t64, f"FreBlock(12) {H}x{W}")
+    for lvl in (0, 1):
+        h, w = H >> lvl, W >> lvl
+        xs = [_rnd(1, n, h, w, seed=h + n) for n in (12, 24, 48)]
+        with torch.no_grad():
+            got = ff(*[dev(t) for t in xs])
+            ref = O.fourier_fuse(*xs, P32(sd_ff), "")
+            t64 = O.fourier_fuse(*[t.double() for t in xs], P64(sd_ff), "")
+        assert_close_cond(got, ref, t64, f"fourier_fuse(84, 12) {h}x{w}")
 
 
 def test_encoder_block_at_baseline_size_vs_oracle(A):

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from common import rel_rms
+from common import fcaffn_ref as _fcaffn_ref, rel_rms
 
 pytestmark = pytest.mark.gpu
 
@@ -30,10 +30,6 @@ def dev(t):
 
 def _rnd(*shape, seed=0):
     return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
-
-
-def _rd(v):
-    return torch.where((v < 1e-10) & (v > -1e-10), torch.full_like(v, 1e-10), v)
 
 
 @pytest.mark.parametrize("H", PLANNED_H)
@@ -72,17 +68,6 @@ def test_cols_inv_polar_matches_ifft(ops, H):
     spec = torch.polar(mag[:, :, :H, :Wf].double(), pha[:, :, :H, :Wf].double())
     ref = torch.fft.ifft(spec, dim=2) * H             # the column pass is unnormalised; irfft_rows carries the scale
     assert rel_rms(z.cpu(), torch.view_as_real(ref)) < 3e-6
-
-
-def _fcaffn_ref(z, amp, pha, wxa, wxp):
-    """float64 restatement of FDN_arch.py:411-418 for the column pass (forward FFT over H, modulation, unnormalised inverse);
-    the phase is formed in float32 like the kernel does, so that large phases compare bin for bin."""
-    Z = torch.fft.fft(torch.view_as_complex(z.double()), dim=2)
-    Zr = torch.complex(_rd(Z.real.float()).double(), _rd(Z.imag.float()).double())
-    A = torch.einsum("ci,bihw->bchw", wxa.double(), amp.double())
-    ph = torch.einsum("ci,bihw->bchw", wxp, pha).double() if wxp.abs().max() < 100 else (wxp[:, 0].view(1, -1, 1, 1) * pha[:, :1]).double()
-    out = Zr * A * torch.polar(torch.ones_like(ph), -ph)
-    return torch.view_as_real(torch.fft.ifft(out, dim=2) * Z.shape[2])
 
 
 @pytest.mark.parametrize("H,C,Wf", [(736, 8, 73), (368, 16, 161), (184, 8, 161), (544, 8, 20), (272, 3, 9), (136, 16, 33), (1088, 8, 41),

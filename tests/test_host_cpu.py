@@ -382,3 +382,130 @@ def test_graph_key_covers_every_routing_switch():
     with torch.no_grad():
         m.weight.add_(1.0)                      # an in-place weight update is seen too
     assert pipeline.weights_signature(m) != base
+
+
+# ---- (ABI 17) the routes of the generic full-image FFT: fdn_fft_route is host arithmetic, the launchers decide by the same code ----
+def _kernel_switch(name, marker):
+    """{radix: lowest BIG at which it has a case} from the `switch (R)` of a device function in csrc/fft2d.hip: `case R: ...` = BIG 0,
+    `case R: if (BIG) ...` = 1, `case R: if (BIG == 2) ...` = 2.  Read from the source, so the check below sees the device-side list."""
+    src = open(os.path.join(ROOT, "fdn-tip2025_amd", "csrc", "fft2d.hip")).read()
+    start = src.index(marker)
+    body = src[start:src.index("\n}\n", start)]
+    cases = {}
+    for r, cond in re.findall(r"case (\d+):\s*(if \(BIG(?: == 2)?\))?", body):
+        cases[int(r)] = 0 if not cond else 2 if "== 2" in cond else 1
+    assert cases, name
+    return cases
+
+
+def _rader_length(p):
+    """Rader applies: p a prime >= 29 and p - 1 a product of the radices with an in-place / BIG-1 register butterfly (2, 3, 5, 7, 17, 23)."""
+    if p < 29 or any(p % f == 0 for f in range(2, int(p ** 0.5) + 1)):
+        return False
+    m = p - 1
+    for f in (2, 3, 5, 7, 17, 23):
+        while m % f == 0:
+            m //= f
+    return m == 1
+
+
+def _lds_bytes(kind, n, rt):
+    """LDS of one workgroup of the generic kernels at the route's tc / rpb (fft2d.hip: launch_cols, fdn_rfft_rows, fdn_irfft_rows)."""
+    if kind == 2:
+        return (n * rt["width"] + n) * 8 if rt["route"] == "inplace" else (2 * n * rt["width"] + n) * 8
+    M = n // 2
+    return (2 * rt["width"] * M + n + (M + rt["width"] if rt["route"] == "rader" else 0)) * 8
+
+
+def test_fft_route_pins_the_lengths_the_gpu_tests_use(lib):
+    from common import FFT_COL_ROUTES, FFT_ROW_ROUTES
+    from fdn_hip import ops
+    for H, (route, big, tc, gather) in FFT_COL_ROUTES.items():
+        rt = ops.fft_route(ops.FFT_COLS, H)
+        assert (rt["route"], rt["big"], rt["width"], rt["gather"]) == (route, big, tc, gather), (H, rt)
+    for W, (route, big, rpb, gather, p) in FFT_ROW_ROUTES.items():
+        rt = ops.fft_route(ops.FFT_ROWS, W)
+        assert (rt["route"], rt["big"], rt["width"], rt["gather"], rt["rader"]) == (route, big, rpb, gather, p), (W, rt)
+        inv = ops.fft_route(ops.FFT_IROWS, W)                   # no Rader on the inverse: a prime half-length gathers
+        assert inv["route"] == ("refused" if route == "refused" else "pingpong") and inv["rader"] == 0, (W, inv)
+        if p:
+            assert inv["gather"] == (p,) and inv["width"] == rpb, (W, inv)
+    # the compile-time plans and where they hand over
+    assert ops.fft_route(ops.FFT_COLS, 736) == {"route": "planned", "big": 0, "width": 8, "rader": 0, "radices": (23, 32), "gather": ()}
+    assert ops.fft_route(ops.FFT_ROWS, 1280)["radices"] == (20, 32) and ops.fft_route(ops.FFT_IROWS, 1120)["radices"] == (35, 16)
+    assert ops.fft_route(ops.FFT_ROWS, 152)["route"] == "pingpong"            # 2 x 19 x 4: not planned (include/fdn_hip.h)
+
+
+def test_fft_route_sweep_invariants(lib):
+    """Every column length 1..4600 and every even row width 2..10260: the plan is a factorisation, an in-place plan uses only radices
+    fft_run_inplace has a case for (at its BIG), register radices imply their BIG tier, a Rader sub-plan has no gather stage, tc / rpb
+    are within their bounds, and a length is refused exactly where the LDS of a workgroup (160 KiB) runs out."""
+    from fdn_hip import ops
+    inplace = _kernel_switch("fft_run_inplace", "__device__ void fft_run_inplace(")
+    reg = _kernel_switch("fft_pass", "__device__ void fft_pass(")
+    reg.update({2: 0, 4: 0})                                   # fft_pass: radix 2 and 4 are the butterflies after the switch
+    assert set(inplace) >= {2, 3, 4, 5, 7}
+    lds_max = 160 * 1024
+    seen = set()
+    for kind, lengths in ((ops.FFT_COLS, range(1, 4601)), (ops.FFT_ROWS, range(2, 10262, 2)), (ops.FFT_IROWS, range(2, 10262, 2))):
+        for n in lengths:
+            rt = ops.fft_route(kind, n)
+            seen.add((kind, rt["route"], rt["big"]))
+            if rt["route"] == "planned":
+                continue
+            N = n if kind == ops.FFT_COLS else n // 2
+            if kind == ops.FFT_COLS:
+                # no column length <= 4096 needs more than tc 2 of ping-pong buffers and the table; 4097 and up do
+                assert (rt["route"] == "refused") == (n > 4096), (n, rt)
+            else:
+                rpb = min(8, max(1, 32 * 1024 // (16 * N)))     # pick_rpb
+                rader = kind == ops.FFT_ROWS and _rader_length(N)
+                need = (2 * rpb * N + n + (N + rpb if rader else 0)) * 8
+                assert (rt["route"] == "refused") == (need > lds_max), (n, rt, need)
+                assert rt["route"] in ("refused", "rader" if rader else "pingpong"), (n, rt)
+                assert rt["route"] == "refused" or rt["width"] == rpb, (n, rt)
+            if rt["route"] == "refused":
+                continue
+            assert _lds_bytes(kind, n, rt) <= lds_max, (kind, n, rt)
+            radices = rt["radices"]
+            prod = 1
+            for r in radices:
+                prod *= r
+            if rt["route"] == "rader":
+                assert kind == ops.FFT_ROWS and rt["rader"] == N and prod == N - 1, (n, rt)
+                assert rt["gather"] == () and all(reg.get(r, 99) <= 1 and r in inplace for r in radices), (n, rt)
+            else:
+                assert prod == N and rt["rader"] == 0, (kind, n, rt)
+            if rt["route"] == "inplace":
+                assert kind == ops.FFT_COLS and rt["width"] in (32, 16, 8) and rt["width"] * n <= 256 * 24, (n, rt)
+                for r in radices:
+                    assert r in inplace and inplace[r] <= rt["big"], f"H = {n}: radix {r} at BIG {rt['big']} has no case in fft_run_inplace {sorted(inplace)}"
+                    assert (n // r) * rt["width"] <= 256 * (36 // r), (n, rt)
+            if kind == ops.FFT_COLS and rt["route"] == "pingpong":
+                assert rt["width"] in (16, 8, 4, 2), (n, rt)
+            if kind != ops.FFT_COLS:
+                assert 1 <= rt["width"] <= 8 and rt["big"] in (0, 1), (n, rt)
+            # BIG tiers: 17 / 23 need BIG >= 1, 13 / 37 / 41 run in registers only on a BIG == 2 column plan; BIG is the least that covers them
+            want_big = 1 if any(r in (17, 23) for r in radices) else 0
+            if kind == ops.FFT_COLS and rt["route"] == "pingpong" and any(r in (13, 37, 41) for r in radices):
+                want_big = 2
+            assert rt["big"] == want_big, (kind, n, rt)
+            if rt["route"] != "inplace":
+                assert rt["gather"] == tuple(r for r in radices if reg.get(r, 99) > rt["big"]), (kind, n, rt)
+    # every route and BIG tier the kernels have is reached by some length
+    for want in [(2, "inplace", 0), (2, "inplace", 1), (2, "pingpong", 0), (2, "pingpong", 1), (2, "pingpong", 2), (2, "refused", 0),
+                 (0, "pingpong", 0), (0, "pingpong", 1), (0, "rader", 0), (0, "rader", 1), (0, "refused", 0), (1, "pingpong", 0), (1, "pingpong", 1)]:
+        assert want in seen, want
+
+
+def test_fft_route_argument_validation(lib):
+    desc = (ctypes.c_int * 37)()
+    assert lib.fdn_fft_route(2, 64, desc, 37) == 0 and desc[0] == 2         # FDN_FFT_INPLACE
+    for kind, n, nd in ((-1, 64, 37), (3, 64, 37), (2, 0, 37), (0, -2, 37), (2, 64, 36), (0, 1282, 5), (0, 35, 37), (1, 9, 37)):
+        assert lib.fdn_fft_route(kind, n, desc, nd) == 1, (kind, n, nd)
+    assert lib.fdn_fft_route(2, 64, None, 37) == 1
+    assert lib.fdn_fft_route(2, 35, desc, 37) == 0                          # odd column lengths are fine
+    from fdn_hip import FdnHipError, ops
+    with pytest.raises(FdnHipError):
+        ops.fft_route(ops.FFT_ROWS, 641)
+    assert ops.fft_route(ops.FFT_COLS, 4097)["route"] == "refused"           # a refusal is an answer, not an error
