@@ -27,6 +27,15 @@ void fdn_note_bf16_launch();                                  // called by every
 bool fdn_matrix_pipe_wide();                                  // default mode: fdn_fdsa_out's level-2 shape on the bf16 pipe too (mode 2 = the ABI-10 default keeps it on fp32 MFMAs)
 bool fdn_occupancy(int* blocks_per_cu, const void* kernel, int threads, size_t lds);   // hipOccupancyMaxActiveBlocksPerMultiprocessor, cached
 
+// Y of ITU-R BT.601 of one B, G, R pixel in [0, 255], the reference's to_y_channel (metric_util.py:34-47 -> matlab_functions.py:207-238,
+// y_only): float32 / 255, float64 dot with (24.966, 128.553, 65.481) + 16, / 255 and back to float32, * 255 in float32 - the reference's
+// own mix of widths.  Shared by fdn_y_channel and fdn_niqe_luma, so the two give the same bits.
+__device__ __forceinline__ float fdn_bgr_to_y(float b, float g, float r) {
+    const double bd = (double)(b / 255.0f), gd = (double)(g / 255.0f), rd = (double)(r / 255.0f);
+    const double y = bd * 24.966 + gd * 128.553 + rd * 65.481 + 16.0;
+    return (float)(y / 255.0) * 255.0f;
+}
+
 __device__ __forceinline__ float gelu_erf(float x) {
     // F.gelu default (erf form), FDN_arch.py:427,438,473
     return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));

@@ -100,14 +100,11 @@ __global__ __launch_bounds__(256) void ssim_final_kernel(const float* __restrict
 }
 
 // ---- Y channel (test_y_channel=True): metric_util.py:34-47 -> matlab_functions.py:207-238 (bgr2ycbcr, y_only) -------------------
-// img [3][H][W] in B, G, R order, range [0, 255]: float32 image / 255, float64 dot with (24.966, 128.553, 65.481) + 16, / 255 and
-// back to float32, * 255 in float32 - the reference's own mix of widths
+// img [3][H][W] in B, G, R order, range [0, 255] (fdn_bgr_to_y, common.hpp)
 __global__ __launch_bounds__(256) void y_channel_kernel(const float* __restrict__ img, float* __restrict__ out, long hw) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= hw) return;
-    const double b = (double)(img[i] / 255.0f), g = (double)(img[hw + i] / 255.0f), r = (double)(img[2 * hw + i] / 255.0f);
-    const double y = b * 24.966 + g * 128.553 + r * 65.481 + 16.0;
-    out[i] = (float)(y / 255.0) * 255.0f;
+    out[i] = fdn_bgr_to_y(img[i], img[hw + i], img[2 * hw + i]);
 }
 
 // ---- 2-D SSIM in float64 (the reference filters float64 arrays with cv2.filter2D): _ssim (:84-116) and _ssim_cly (:199-240) -----

@@ -2,10 +2,15 @@
 (:243-328) with all their branches - the default 3-D Gaussian SSIM (`ssim3d=True`, :163-197), the 2-D one (`ssim3d=False`, `_ssim`
 :84-116) and the Y-channel variants (`test_y_channel=True`: `to_y_channel` + `_ssim_cly` :199-240) - for (C,H,W) or (1,C,H,W) float32
 ROCm tensors.  With `test_y_channel` the channels must be in B, G, R order and the range [0, 255], as the reference's callers pass
-them (`tensor2img(..., rgb2bgr=True)`).  No CPU fallback."""
+them (`tensor2img(..., rgb2bgr=True)`).  No CPU fallback.
+
+The same package's no-reference metric, `calculate_niqe` (basicsr/metrics/niqe.py:67-205), is here too: the plane, the MSCN planes
+and the per-block features on the GPU (csrc/niqe.hip), the 36-feature MVG fit on the host in float64 with the reference's own calls."""
 import ctypes
 import math
+import os
 
+import numpy as np
 import torch
 
 from . import FdnHipError, check, lib, stream
@@ -82,3 +87,135 @@ def calculate_ssim(img1, img2, crop_border=0, test_y_channel=False, ssim3d=True)
     acc = torch.zeros(1, dtype=torch.float64, device=a.device)
     check(lib().fdn_ssim3d(_ptr(a), _ptr(b), C, H, W, ctypes.c_float(max_value), _ptr(ws), _ptr(acc), stream()), "fdn_ssim3d")
     return float(acc.item()) / a.numel()
+
+
+# ---- NIQE (basicsr/metrics/niqe.py) ------------------------------------------------------------------------------------------------------
+NIQE_BLOCK = 96                                                                                       # block_size_h / _w (:70-71)
+_LUMA_MODE = {"y": 0, "gray": 1}
+_niqe_tables_dev = {}       # device -> float64 tensor [4][9801] of fdn_niqe_features: built once per device, as ops._fdsa_scratch is
+
+
+def niqe_tables():
+    """The AGGD search tables of estimate_aggd_param (:21-37), float64 [4][9801] on the host: gam = np.arange(0.2, 10.001, 0.001),
+    r_gam = gamma(2/a)^2 / (gamma(1/a) gamma(3/a)) with the reference's 1/a * 2, 1/a * 3, then sqrt(gamma(1/a) / gamma(3/a)) and
+    gamma(2/a) / gamma(1/a) as :35-36 and :61 form them.  math.gamma, so that the product does not depend on scipy."""
+    gam = np.arange(0.2, 10.001, 0.001)
+    rec = np.reciprocal(gam)
+    g = math.gamma
+    r_gam = np.array([g(r * 2) * g(r * 2) / (g(r) * g(r * 3)) for r in rec.tolist()])
+    beta = np.array([math.sqrt(g(1 / a) / g(3 / a)) for a in gam.tolist()])
+    mean = np.array([g(2 / a) / g(1 / a) for a in gam.tolist()])
+    return np.stack([gam, r_gam, beta, mean])
+
+
+def _niqe_tables_on(device):
+    t = _niqe_tables_dev.get(str(device))
+    if t is None:
+        t = _niqe_tables_dev[str(device)] = torch.from_numpy(niqe_tables()).to(device)
+    return t
+
+
+def niqe_params(params=None):
+    """(mu_pris_param [1,36], cov_pris_param [36,36], gaussian_window [7,7]), float64.  params: a path to niqe_pris_params.npz, a
+    mapping with those three keys, or None: basicsr/metrics/niqe_pris_params.npz of the reference checkout behind this package, found
+    along `basicsr.__path__`."""
+    if params is None:
+        import basicsr
+        for d in basicsr.__path__:
+            f = os.path.join(d, "metrics", "niqe_pris_params.npz")
+            if os.path.isfile(f):
+                params = f
+                break
+        else:
+            raise FdnHipError("calculate_niqe: no basicsr/metrics/niqe_pris_params.npz along basicsr.__path__ (put the reference checkout "
+                              "on sys.path after this package, or pass params=<path to niqe_pris_params.npz or a mapping>)")
+    if isinstance(params, (str, os.PathLike)):
+        with np.load(params) as z:
+            params = {k: z[k] for k in z.files}
+    try:
+        mu = np.asarray(params["mu_pris_param"], dtype=np.float64).reshape(1, 36)
+        cov = np.asarray(params["cov_pris_param"], dtype=np.float64).reshape(36, 36)
+        win = np.asarray(params["gaussian_window"], dtype=np.float64)
+    except (KeyError, ValueError) as e:
+        raise FdnHipError(f"calculate_niqe: params need mu_pris_param [1,36], cov_pris_param [36,36] and gaussian_window [7,7] ({e})")
+    if win.shape != (7, 7):
+        raise FdnHipError(f"calculate_niqe: gaussian_window must be 7x7, got {win.shape}")
+    return mu, cov, win
+
+
+def niqe_features(img, crop_border=0, input_order="CHW", convert_to="y", window=None):
+    """The GPU part of calculate_niqe for (H,W) ('HW'), (C,H,W) or (B,C,H,W) float32 ROCm tensors in [0, 255], B, G, R order.
+    Returns a dict of device tensors: "plane" [B][H][W] (the scored plane, cut to whole 96x96 blocks), "mscn1" [B][H][W],
+    "mscn2" [B][H/2][W/2] and "feats" [2][B][nblocks][18] float64 (scale 1, scale 2; blocks idx_w outer, idx_h inner)."""
+    if not isinstance(img, torch.Tensor) or not img.is_cuda or img.dtype != torch.float32:
+        raise FdnHipError("calculate_niqe takes float32 ROCm tensors")
+    if input_order == "HW":
+        if img.dim() != 2:
+            raise FdnHipError(f"input_order='HW' needs an (H, W) tensor, got {tuple(img.shape)}")
+        x, mode = img.reshape(1, 1, *img.shape), 2
+    elif input_order == "CHW":
+        if img.dim() not in (3, 4):
+            raise FdnHipError(f"input_order='CHW' needs a (C,H,W) or (B,C,H,W) tensor, got {tuple(img.shape)}")
+        x = img if img.dim() == 4 else img.unsqueeze(0)
+        if convert_to not in _LUMA_MODE:
+            raise FdnHipError(f"convert_to must be 'y' or 'gray', got {convert_to!r}")
+        mode = _LUMA_MODE[convert_to]
+        if x.shape[1] != 3 and not (x.shape[1] == 1 and mode == 0):
+            raise FdnHipError(f"convert_to={convert_to!r} needs 3 channels (B, G, R){' or 1' if mode == 0 else ''}, got {x.shape[1]}")
+    else:
+        raise FdnHipError(f"input_order must be 'HW' or 'CHW', got {input_order!r}")
+    B, C, Hs, Ws = x.shape
+    cb = int(crop_border)
+    if cb < 0:
+        raise FdnHipError("crop_border must be >= 0")
+    nbh, nbw = (Hs - 2 * cb) // NIQE_BLOCK, (Ws - 2 * cb) // NIQE_BLOCK
+    if nbh < 1 or nbw < 1:
+        raise FdnHipError(f"calculate_niqe: {Hs}x{Ws} with crop_border={cb} holds no whole {NIQE_BLOCK}x{NIQE_BLOCK} block")
+    if window is None:
+        window = niqe_params()[2]
+    win = np.ascontiguousarray(window, dtype=np.float64).reshape(49)
+    x = x.contiguous()
+    H, W = nbh * NIQE_BLOCK, nbw * NIQE_BLOCK
+    dev = x.device
+    plane = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    mscn1 = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    mscn2 = torch.empty((B, H // 2, W // 2), dtype=torch.float32, device=dev)
+    feats = torch.empty((2, B, nbh * nbw, 18), dtype=torch.float64, device=dev)
+    tables = _niqe_tables_on(dev)
+    l, s = lib(), stream()
+    wp = win.ctypes.data_as(ctypes.c_void_p)
+    check(l.fdn_niqe_luma(_ptr(x), _ptr(plane), B, C, Hs, Ws, cb, cb, H, W, mode, s), "fdn_niqe_luma")
+    check(l.fdn_niqe_mscn(_ptr(plane), _ptr(mscn1), B, H, W, 0, wp, s), "fdn_niqe_mscn")
+    check(l.fdn_niqe_mscn(_ptr(plane), _ptr(mscn2), B, H // 2, W // 2, 1, wp, s), "fdn_niqe_mscn")
+    ntab = tables.shape[1]
+    check(l.fdn_niqe_features(_ptr(mscn1), _ptr(feats[0]), B, H, W, NIQE_BLOCK, _ptr(tables), ntab, s), "fdn_niqe_features")
+    check(l.fdn_niqe_features(_ptr(mscn2), _ptr(feats[1]), B, H // 2, W // 2, NIQE_BLOCK // 2, _ptr(tables), ntab, s), "fdn_niqe_features")
+    return {"plane": plane, "mscn1": mscn1, "mscn2": mscn2, "feats": feats}
+
+
+def niqe_score(distparam, mu_pris_param, cov_pris_param):
+    """The MVG fit of niqe() (:141-153) on the host in float64, with the reference's calls, for distparam [nblocks][36].  A row with a
+    NaN drops out of the covariance but its other entries stay in the mean, as np.nanmean / the complete-row np.cov there do."""
+    complete = distparam[~np.isnan(distparam).any(axis=1)]
+    if complete.shape[0] < 2:
+        raise FdnHipError(f"calculate_niqe: {complete.shape[0]} of {distparam.shape[0]} blocks have complete features (a flat image?); "
+                          "the covariance needs at least 2")
+    mu_distparam = np.nanmean(distparam, axis=0)
+    cov_distparam = np.cov(complete, rowvar=False)
+    invcov_param = np.linalg.pinv((cov_pris_param + cov_distparam) / 2)
+    quality = np.matmul(np.matmul((mu_pris_param - mu_distparam), invcov_param), np.transpose((mu_pris_param - mu_distparam)))
+    q = float(np.sqrt(quality).item())
+    if not math.isfinite(q):
+        raise FdnHipError(f"calculate_niqe: the score is not finite ({q})")
+    return q
+
+
+def calculate_niqe(img, crop_border=0, input_order="CHW", convert_to="y", params=None):
+    """NIQE of calculate_niqe (basicsr/metrics/niqe.py:158-205) for float32 ROCm tensors in [0, 255], channels B, G, R.
+    (H,W) with input_order='HW', (C,H,W) or (1,C,H,W) -> a float; (B,C,H,W) with B > 1 -> a list of B floats (one launch per kernel
+    for the batch).  params: see niqe_params; convert_to: 'y' (Y of BT.601) or 'gray' (cv2.cvtColor BGR2GRAY)."""
+    mu, cov, win = niqe_params(params)
+    r = niqe_features(img, crop_border, input_order, convert_to, window=win)
+    f = r["feats"].cpu().numpy()                                                                      # [2][B][nblocks][18]
+    scores = [niqe_score(np.concatenate([f[0, b], f[1, b]], axis=1), mu, cov) for b in range(f.shape[1])]
+    return scores if (img.dim() == 4 and img.shape[0] > 1) else scores[0]

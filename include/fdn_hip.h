@@ -36,7 +36,7 @@ enum { FDN_PRO_NONE = 0, FDN_PRO_LN = 1, FDN_PRO_LN3_GATE = 2, FDN_PRO_LN_MULADD
 enum { FDN_EPI_NONE = 0, FDN_EPI_RES = 1, FDN_EPI_MULADD = 2 };
 enum { FDN_RS_BILINEAR_HALF = 0, FDN_RS_BILINEAR_X2 = 1, FDN_RS_NEAREST_HALF = 2, FDN_RS_NEAREST_X2 = 3, FDN_RS_PIXEL_UNSHUFFLE = 4 };
 
-/* library version / build info: returns the ABI version (bumped on any signature change; 17 since fdn_fft_route) */
+/* library version / build info: returns the ABI version (bumped on any signature change; 18 since the fdn_niqe_* entry points) */
 int fdn_abi_version(void);
 const char* fdn_error_string(int code);
 /* Diagnostic switch, process-wide, default 0 = every matrix product that has a split-bf16 form runs on the bf16 matrix pipe
@@ -389,6 +389,26 @@ int fdn_ssim3d(const float* a, const float* b, int C, int H, int W, float max_va
 int fdn_y_channel(const float* img_bgr, float* out, int H, int W, fdn_stream_t stream);
 int fdn_ssim2d(const float* a, const float* b, int C, int H, int W, float max_value, int replicate_no_crop, double* ws,
                double* out_sum, fdn_stream_t stream);
+/* ABI 18.  NIQE, the no-reference metric of the same package (basicsr/metrics/niqe.py:67-205), up to the per-block features; the MVG
+ * fit of :141-153 (nanmean, cov over complete rows, pinv, quadratic form) is the caller's, on the host in float64.
+ * fdn_niqe_luma: src [B][C][Hs][Ws] (B, G, R order, range [0, 255]) -> out [B][H][W], the window at (top, left) of the plane calculate_niqe
+ *   scores (:192-203; the crop_border and the cut to whole 96x96 blocks from the top-left, :104-107, are the window): mode 0 =
+ *   to_y_channel (C = 3: the Y of fdn_y_channel, bit for bit; C = 1: (x / 255) * 255 in float32, metric_util.py:43-47), 1 =
+ *   cv2.cvtColor(img / 255., COLOR_BGR2GRAY) * 255. (:199; C = 3, 0.114 B + 0.587 G + 0.299 R in float32), 2 = the plane as it is
+ *   (input_order 'HW', C = 1).
+ * fdn_niqe_mscn: the MSCN plane of one scale (:111-117), mscn [B][H][W] = (img - mu) / (sigma + 1) with mu = convolve(img, w,
+ *   mode='nearest') and sigma = sqrt(|convolve(img^2, w) - mu^2|): the 49 taps summed in fp64 and stored as fp32, as scipy does, the
+ *   rest in fp32.  window49 = HOST pointer to the 7x7 gaussian_window (row-major float64).  half = 0: img = src [B][H][W]; half = 1:
+ *   src is the scale-1 plane [B][2H][2W] and img its cv2.resize(img / 255., (W, H)) * 255. (:134-138), the 2x2 mean at this size.
+ * fdn_niqe_features: per 96/scale block (block = 96 or 48), in the reference's order (idx_w outer, idx_h inner, :120-128), the 18
+ *   features of compute_feature (:40-64) -> feats [B][(H/block)(W/block)][18] float64.  tables = device float64 [4][ntab]: gam =
+ *   np.arange(0.2, 10.001, 0.001), r_gam (:21-24), sqrt(gamma(1/gam) / gamma(3/gam)) and gamma(2/gam) / gamma(1/gam).  A block with no
+ *   negative (or no positive) coefficient gets alpha = gam[0] and NaN betas, as np.argmin over NaN gives (:31-33). */
+int fdn_niqe_luma(const float* src, float* out, int B, int C, int Hs, int Ws, int top, int left, int H, int W, int mode,
+                  fdn_stream_t stream);
+int fdn_niqe_mscn(const float* src, float* mscn, int B, int H, int W, int half, const double* window49, fdn_stream_t stream);
+int fdn_niqe_features(const float* mscn, double* feats, int B, int H, int W, int block, const double* tables, int ntab,
+                      fdn_stream_t stream);
 
 #ifdef __cplusplus
 }

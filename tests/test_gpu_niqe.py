@@ -1,0 +1,174 @@
+"""NIQE on the GPU (csrc/niqe.hip through fdn_hip.metrics.calculate_niqe) against the reference's own numbers (tests/golden/niqe.npz,
+make_golden_niqe.py) and, at sizes the fixture does not hold, against the numpy restatement tests/niqe_ref.py.
+
+Tolerances (what an MI355X gave in brackets).  Against the reference: the plane bit for bit; MSCN within 1e-6 absolute (bit-identical);
+per fit the alpha table index within +-1 of the reference's and identical for >= 99 % of a case's fits (one fit of "crop" is one index
+off: the reference forms rhatnorm from float32 means, the kernel from fp64 sums); the other features within 1e-6 relative where the index
+agrees (1.5e-7), the AGGD mean relative to the size of the two betas it is the difference of (niqe_ref.compare_feats: in some blocks they
+cancel to a few parts in 1e3); the score within 1e-5 relative (1.5e-6, "crop").  Against the restatement, which takes the same fp64 sums:
+features and score within 1e-10 relative (5e-16)."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import niqe_ref as R
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+FEAT_RTOL, SCORE_RTOL, MSCN_ATOL = 1e-6, 1e-5, 1e-6
+REF_RTOL = 1e-10            # GPU against tests/niqe_ref.py
+TAB = R.tables()
+
+
+@pytest.fixture(scope="module")
+def M():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a ROCm GPU")
+    import fdn_hip
+    fdn_hip.lib()   # fail loudly if the HIP extension is not built
+    from fdn_hip import metrics
+    return metrics
+
+
+@pytest.fixture(scope="module")
+def fx():
+    return R.load_fixture(HERE)
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a).astype(np.float32)).to("cuda:0")
+
+
+def check_feats(got, want, name, rtol=FEAT_RTOL):
+    """got, want [nblocks][18]; returns whether each fit's alpha index is identical"""
+    assert got.shape == want.shape, name
+    assert np.array_equal(np.isnan(got), np.isnan(want)), name
+    same, dmax, worst = R.compare_feats(got, want, TAB)
+    assert dmax <= 1, (name, dmax)
+    assert worst <= rtol, (name, worst)
+    print(f"{name}: alpha index identical {same.mean():.4f}, worst relative feature error {worst:.2e}")
+    return same
+
+
+@pytest.mark.parametrize("name", ["tex", "crop", "dark", "hw", "gray", "big", "planes"])
+def test_against_reference(M, fx, name):
+    z, cases, params, image = fx
+    c = cases[name]
+    x = dev(image(name))
+    r = M.niqe_features(x, c["crop_border"], c["input_order"], c["convert_to"], window=params["gaussian_window"])
+    torch.cuda.synchronize()
+    f = r["feats"].cpu().numpy()
+    same = np.concatenate([check_feats(f[0, 0], z[f"{name}_feat1"], f"{name} scale 1"),
+                           check_feats(f[1, 0], z[f"{name}_feat2"], f"{name} scale 2")])
+    assert same.mean() >= 0.99, (name, same.mean())
+    q = M.calculate_niqe(x, c["crop_border"], c["input_order"], c["convert_to"], params=params)
+    assert isinstance(q, float)
+    print(f"{name}: NIQE {q:.9f} reference {c['niqe']:.9f} relative {abs(q / c['niqe'] - 1):.2e}")
+    assert abs(q / c["niqe"] - 1) <= SCORE_RTOL
+    if name == "planes":
+        assert torch.equal(r["plane"][0].cpu(), torch.from_numpy(z["planes_y"]))
+        for s in (1, 2):
+            got, want = r[f"mscn{s}"][0].cpu().numpy(), z[f"planes_mscn{s}"]
+            err = np.abs(got - want).max()
+            print(f"planes MSCN scale {s}: max |error| {err:.2e}, bit-identical {(got == want).mean():.6f}")
+            assert err <= MSCN_ATOL
+    if name == "dark":                   # rows with a NaN drop out of the covariance; their alpha = 0.2 stays in the mean
+        dist = np.concatenate([f[0, 0], f[1, 0]], axis=1)
+        assert np.nonzero(np.isnan(dist).any(axis=1))[0].tolist() == c["dropped_rows"]
+        want = np.concatenate([z["dark_feat1"], z["dark_feat2"]], axis=1)
+        quirk = np.isnan(want[:, [1, 19]]) & (want[:, [0, 18]] == np.arange(0.2, 10.001, 0.001)[0])
+        assert quirk.any()
+        assert np.array_equal(dist[:, [0, 18]][quirk], want[:, [0, 18]][quirk])
+
+
+def test_plane_is_fdn_y_channel(M, fx):
+    z, _, params, image = fx
+    x = dev(image("big"))
+    r = M.niqe_features(x, window=params["gaussian_window"])
+    y = M.to_y_channel(x)[0, :r["plane"].shape[1], :r["plane"].shape[2]]
+    assert torch.equal(r["plane"][0], y)
+
+
+def test_batch_equals_single_calls(M, fx):
+    _, _, params, image = fx
+    big = image("big")
+    imgs = [big[:, y:y + 288, x:x + 480] for y, x in ((0, 0), (100, 50), (192, 192), (37, 101))]
+    batch = M.calculate_niqe(dev(np.stack(imgs)), params=params)
+    single = [M.calculate_niqe(dev(a), params=params) for a in imgs]
+    assert isinstance(batch, list) and len(batch) == 4
+    assert batch == single
+    assert M.calculate_niqe(dev(imgs[0][None]), params=params) == single[0]          # (1,C,H,W) -> a float
+
+
+def frame(seed, h, w):
+    g = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    base = 100 + 50 * np.sin(xx / (20 + 10 * seed)) * np.cos(yy / 33.0) + 30 * ((xx // 64 + yy // 48) % 2)
+    img = np.stack([base * 0.8 + 20, base, base * 0.9]) + g.normal(0, 6, (3, h, w))
+    return np.clip(np.rint(img), 0, 255).astype(np.uint8)
+
+
+def test_736x1280_batch_against_restatement(M, fx):
+    _, _, params, _ = fx
+    imgs = [frame(s, 736, 1280) for s in (1, 2)]
+    x = dev(np.stack(imgs))
+    r = M.niqe_features(x, window=params["gaussian_window"])
+    q = M.calculate_niqe(x, params=params)
+    f = r["feats"].cpu().numpy()
+    for b, img in enumerate(imgs):
+        want, d = R.niqe(img, params, tab=TAB)
+        assert torch.equal(r["plane"][b].cpu(), torch.from_numpy(d["plane"]))
+        for s in (1, 2):
+            assert np.abs(r[f"mscn{s}"][b].cpu().numpy() - d[f"mscn{s}"]).max() <= MSCN_ATOL
+        same = np.concatenate([check_feats(f[0, b], d["feat1"], f"736x1280[{b}] scale 1", REF_RTOL),
+                               check_feats(f[1, b], d["feat2"], f"736x1280[{b}] scale 2", REF_RTOL)])
+        assert same.mean() >= 0.99
+        print(f"736x1280[{b}]: NIQE {q[b]:.12f} restatement {want:.12f}")
+        assert abs(q[b] / want - 1) <= REF_RTOL
+
+
+def test_errors(M, fx):
+    _, _, params, image = fx
+    x = dev(image("tex"))
+    with pytest.raises(M.FdnHipError, match="block"):
+        M.calculate_niqe(x[:, :95, :], params=params)                              # no whole block
+    with pytest.raises(M.FdnHipError, match="block"):
+        M.calculate_niqe(x[:, :100, :], crop_border=4, params=params)              # none after the crop
+    with pytest.raises(M.FdnHipError, match="complete"):
+        M.calculate_niqe(torch.zeros(3, 192, 192, device="cuda:0"), params=params)  # all black: no complete feature row
+    with pytest.raises(M.FdnHipError, match="float32"):
+        M.calculate_niqe(x.double(), params=params)
+    with pytest.raises(M.FdnHipError, match="float32"):
+        M.calculate_niqe(x.cpu(), params=params)
+    with pytest.raises(M.FdnHipError):
+        M.calculate_niqe(x, input_order="HWC", params=params)
+    with pytest.raises(M.FdnHipError):
+        M.calculate_niqe(x[:1], convert_to="gray", params=params)
+    with pytest.raises(M.FdnHipError):
+        M.calculate_niqe(x[0], input_order="CHW", params=params)
+
+
+def test_cli_end_to_end(M, fx, tmp_path):
+    from PIL import Image
+    _, _, _, image = fx
+    big = image("big")
+    imgs = {"a": big[:, :288, :480], "b": big[:, 96:384, 100:580], "c": big[:, :, :]}   # two of one size, one of another
+    for k, a in imgs.items():
+        Image.fromarray(np.ascontiguousarray(a[::-1].transpose(1, 2, 0))).save(tmp_path / f"{k}.png")   # B, G, R -> an RGB file
+    p = os.path.join(HERE, "golden", "niqe_pris_params.npz")
+    cmd = [sys.executable, os.path.join(ROOT, "fdn-tip2025_amd", "calculate_niqe.py"), "--input", str(tmp_path / "*.png"), "--params", p,
+           "--batch", "2"]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr
+    lines = out.stdout.splitlines()
+    print(out.stdout)
+    want = [M.calculate_niqe(dev(imgs[k]), params=p) for k in "abc"]
+    for i, k in enumerate("abc"):
+        assert lines[i] == f'{i+1:3d}: {k:25}. \tNIQE: {want[i]:.6f}'
+    assert lines[3] == str(tmp_path / "*.png")
+    assert lines[4] == f'Average: NIQE: {sum(want) / 3:.6f}'
