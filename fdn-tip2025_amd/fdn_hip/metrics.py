@@ -5,7 +5,9 @@ ROCm tensors.  With `test_y_channel` the channels must be in B, G, R order and t
 them (`tensor2img(..., rgb2bgr=True)`).  No CPU fallback.
 
 The same package's no-reference metric, `calculate_niqe` (basicsr/metrics/niqe.py:67-205), is here too: the plane, the MSCN planes
-and the per-block features on the GPU (csrc/niqe.hip), the 36-feature MVG fit on the host in float64 with the reference's own calls."""
+and the per-block features on the GPU (csrc/niqe.hip), the 36-feature MVG fit on the host in float64 with the reference's own calls.
+
+`calculate_lpips` is scripts/metrics/calculate_lpips.py's per-image step: LPIPS v0.1 (fdn_hip.lpips, csrc/lpips.hip) of 8-bit images."""
 import ctypes
 import math
 import os
@@ -219,3 +221,45 @@ def calculate_niqe(img, crop_border=0, input_order="CHW", convert_to="y", params
     f = r["feats"].cpu().numpy()                                                                      # [2][B][nblocks][18]
     scores = [niqe_score(np.concatenate([f[0, b], f[1, b]], axis=1), mu, cov) for b in range(f.shape[1])]
     return scores if (img.dim() == 4 and img.shape[0] > 1) else scores[0]
+
+
+# ---- LPIPS (scripts/metrics/calculate_lpips.py: lpips.LPIPS(net='vgg'), version 0.1) --------------------------------------------------------
+_lpips_models = {}          # (net, weights path, lin path, device) -> LPIPS: the weights are loaded once per file and device
+
+
+def lpips_model(net="vgg", weights=None, lin_weights=None, device=None):
+    """fdn_hip.lpips.LPIPS for these weights; built once per (net, files, device) when the weights are given as paths"""
+    from .lpips import LPIPS
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    paths = all(w is None or isinstance(w, (str, os.PathLike)) for w in (weights, lin_weights))
+    if not paths:
+        return LPIPS(net, weights, lin_weights, dev)
+    key = (net, None if weights is None else os.path.abspath(weights), None if lin_weights is None else os.path.abspath(lin_weights), str(dev))
+    m = _lpips_models.get(key)
+    if m is None:
+        m = _lpips_models[key] = LPIPS(net, weights, lin_weights, dev)
+    return m
+
+
+def _u8_images(img, dev):
+    if isinstance(img, np.ndarray):
+        img = torch.from_numpy(np.ascontiguousarray(img))
+    if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or img.dim() not in (3, 4) or img.shape[-1] != 3:
+        raise FdnHipError("calculate_lpips takes uint8 images (H,W,3) or (B,H,W,3), numpy arrays or tensors, got "
+                          f"{getattr(img, 'dtype', type(img).__name__)} {tuple(getattr(img, 'shape', ()))}")
+    return (img if img.dim() == 4 else img.unsqueeze(0)).to(dev).contiguous()
+
+
+def calculate_lpips(img1, img2, net="vgg", model=None, weights=None, lin_weights=None, bgr=True, device=None, per_layer=False):
+    """LPIPS v0.1 of calculate_lpips.py (:44-54) for 8-bit images: (H,W,3) or (B,H,W,3) uint8 numpy arrays or tensors, channels B, G, R
+    as cv2.imread gives them (bgr=False: R, G, B as PIL gives them).  img1 is lpips' in0 (the restored image in the reference script),
+    img2 in1 (the ground truth); the metric is symmetric.  model: an fdn_hip.lpips.LPIPS, else one is built (once per file) from net,
+    weights and lin_weights.  -> a float for one pair, a list of B floats for a batch (one backbone pass for all 2B images);
+    per_layer=True gives the five heads' terms instead ([5] / [B][5] lists)."""
+    if tuple(img1.shape) != tuple(img2.shape):
+        raise FdnHipError(f"Image shapes are different: {tuple(img1.shape)}, {tuple(img2.shape)}.")      # as psnr_ssim.py:30
+    if model is None:
+        model = lpips_model(net, weights, lin_weights, device)
+    a, b = _u8_images(img1, model.device), _u8_images(img2, model.device)
+    d = model.from_u8(a, b, bgr=bgr, per_layer=per_layer).cpu().tolist()
+    return d if len(img1.shape) == 4 and img1.shape[0] > 1 else d[0]

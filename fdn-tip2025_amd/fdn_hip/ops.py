@@ -611,6 +611,16 @@ def conv2d(x, w, bias=None, stride=1, pad=0, act=ACT_NONE, res=None, res_before_
     return out
 
 
+def maxpool2d(x, k, s):
+    """nn.MaxPool2d(k, s): no padding, floor mode (the LPIPS backbones)"""
+    B, C, H, W = x.shape
+    if H < k or W < k:
+        raise FdnHipError(f"maxpool2d: {H}x{W} is smaller than the {k}x{k} window")
+    out = torch.empty((B, C, (H - k) // s + 1, (W - k) // s + 1), device=x.device, dtype=torch.float32)
+    check(lib().fdn_maxpool2d(_flat(x, "x"), _flat(out, "out"), ctypes.c_long(B * C), H, W, k, s, stream()), "fdn_maxpool2d")
+    return out
+
+
 def conv_transpose4x4s2(x, w, bias, act):
     B, Cin, H, W = x.shape
     Cout = w.shape[1]

@@ -36,7 +36,7 @@ enum { FDN_PRO_NONE = 0, FDN_PRO_LN = 1, FDN_PRO_LN3_GATE = 2, FDN_PRO_LN_MULADD
 enum { FDN_EPI_NONE = 0, FDN_EPI_RES = 1, FDN_EPI_MULADD = 2 };
 enum { FDN_RS_BILINEAR_HALF = 0, FDN_RS_BILINEAR_X2 = 1, FDN_RS_NEAREST_HALF = 2, FDN_RS_NEAREST_X2 = 3, FDN_RS_PIXEL_UNSHUFFLE = 4 };
 
-/* library version / build info: returns the ABI version (bumped on any signature change; 18 since the fdn_niqe_* entry points) */
+/* library version / build info: returns the ABI version (bumped on any signature change; 19 since the fdn_lpips_* entry points and fdn_maxpool2d) */
 int fdn_abi_version(void);
 const char* fdn_error_string(int code);
 /* Diagnostic switch, process-wide, default 0 = every matrix product that has a split-bf16 form runs on the bf16 matrix pipe
@@ -409,6 +409,26 @@ int fdn_niqe_luma(const float* src, float* out, int B, int C, int Hs, int Ws, in
 int fdn_niqe_mscn(const float* src, float* mscn, int B, int H, int W, int half, const double* window49, fdn_stream_t stream);
 int fdn_niqe_features(const float* mscn, double* feats, int B, int H, int W, int block, const double* tables, int ntab,
                       fdn_stream_t stream);
+/* ABI 19.  LPIPS v0.1 (Zhang et al. 2018; the `lpips` package's LPIPS(net='vgg' | 'alex', version='0.1') in eval mode, which the
+ * reference's scripts/metrics/calculate_lpips.py calls) around its backbone; the backbone's convs are fdn_conv2d with FDN_ACT_RELU.
+ * fdn_lpips_prep_u8: src [B][H][W][3] uint8 (bgr = 1: B, G, R as cv2.imread gives; 0: R, G, B) -> out [B][3][H][W] in R, G, B order,
+ *   the scaling layer's output, in the float32 op order of calculate_lpips.py: v = x / 255, v = (v - .5) / .5 (torchvision normalize),
+ *   v = (v - shift_c) / scale_c with shift = (-.030, -.088, -.188), scale = (.458, .448, .450) (float32).  Bit for bit torch float32.
+ * fdn_lpips_prep_f32: x [B][3][H][W] float -> out (same shape, may not alias): from01 = 1: v = 2 x - 1 (lpips' normalize=True, an
+ *   image in [0, 1] such as FDN's output), 0: v = x (already in [-1, 1]); then the scaling layer as above.
+ * fdn_maxpool2d: nn.MaxPool2d(k, s) with no padding, floor mode: x [planes][H][W] -> out [planes][(H-k)/s+1][(W-k)/s+1]; a NaN in the
+ *   window wins, as in torch.  H, W >= k.
+ * fdn_lpips_layer: one tap for B pairs.  f [2B][C][H][W] holds the features of the B in0 images, then of the B in1 images; w [C] the
+ *   tap's linear head (linK.model.1.weight).  out[b] = (accumulate ? out[b] : 0) + mean_{h,w} sum_c w_c (f0_c / (|f0| + 1e-10) -
+ *   f1_c / (|f1| + 1e-10))^2, |f| the channel norm of a pixel.  Two passes over the channels in fp64 (norms, then the normalised
+ *   difference: no expanded form that cancels for near-identical images); fixed-order partials in ws and a fixed-order final sum, so
+ *   repeated calls, swapping the pair and the pair's place in the batch give the same bits.  ws: B * FDN_LPIPS_PARTS doubles. */
+enum { FDN_LPIPS_PARTS = 1024 };
+int fdn_lpips_prep_u8(const unsigned char* src, float* out, int B, int H, int W, int bgr, fdn_stream_t stream);
+int fdn_lpips_prep_f32(const float* x, float* out, int B, int H, int W, int from01, fdn_stream_t stream);
+int fdn_maxpool2d(const float* x, float* out, long planes, int H, int W, int k, int s, fdn_stream_t stream);
+int fdn_lpips_layer(const float* f, const float* w, double* out, int B, int C, int H, int W, int accumulate, double* ws,
+                    fdn_stream_t stream);
 
 #ifdef __cplusplus
 }
