@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """FDN inference bench on MI355X:  images/s of the whole LPNet -> FDN forward (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: this process spawns one rank per GPU itself)
+    python bench.py --gpus N --steps K --warmup W [--full]  (N > 1: this process spawns one rank per GPU itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W             (the driver's launch; WORLD_SIZE must equal --gpus)
 
@@ -9,15 +9,20 @@ A step = one pass of the hot path over one batch: config 2 of BASELINE.json, 8 s
 1280x720 reflect-padded to 736x1280, fp32, already resident in HBM.  N GPUs = N shards of 8 images
 (the batch shards embarrassingly) -> "scaling": "weak".  With N > 1 the global batch lives
 on rank 0 and the timed region contains the RCCL scatter of the inputs and gather of the outputs that
-north_star names (BASELINE.json configs[3] at N = 8: 64 images, 8 x 8); the same K steps without the
-collectives are reported beside it ("without_collectives").  --dtype bf16 --height 1080 --width 1920
---batch 4 is configs[2].  Weights are deterministic synthetic (the trained FDN checkpoint is absent from
-the reference checkout); LPNet uses the real LPNet_lolblur weights when tests/golden has them.
+north_star names (BASELINE.json configs[3] at N = 8: 64 images, 8 x 8).  --dtype bf16 --height 1080
+--width 1920 --batch 4 is configs[2].  Weights are deterministic synthetic (the trained FDN checkpoint is
+absent from the reference checkout); LPNet uses the real LPNet_lolblur weights when tests/golden has them.
 
-Extra JSON objects: "roofline" = the dominant INDIVIDUAL kernel (entry point at one shape = one rocprof
-kernel) against its own bound, timed live with HIP events on the launch stream in an instrumented
-single-stream forward; "top_kernels" = the three largest, each against its own bound; "cpu_baseline" =
-the CPU oracle on a bounded sample.
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: nothing else.
+--full then measures and checks what the headline figure does not need, each in runs of its own after the
+timed steps (the --no-* options leave parts of it out):
+  "roofline" = the dominant INDIVIDUAL kernel (entry point at one shape = one rocprof kernel) against its own
+  bound, timed live with HIP events on the launch stream in an instrumented single-stream forward;
+  "top_kernels" = the three largest, each against its own bound; "cpu_baseline" = the CPU oracle on a bounded
+  sample (and ONE real 736 x 1280 forward at the headline shape); "parity" = the timed graph replayed on the
+  configs[1] fixture frame against the reference's forward; "other_configs" = configs[2] and configs[4] beside
+  the headline shape; "without_collectives" (N > 1) = the same K steps with every shard already resident.
+Without --full these are null (without_collectives: absent), and whole_path has no committed-profile figures.
 """
 import argparse
 import ctypes
@@ -674,21 +679,24 @@ def main():
     ap.add_argument("--resample-upsample", action="store_true", help="A/B: Upsample as fdn_resample x2 + the 3x3 conv instead of the low-resolution 1x1 conv per tap + fdn_upconv_gather")
     ap.add_argument("--aff-resized", action="store_true", help="A/B: MAR's fourier_fuse on nearest-resized copies (one 84-channel 1x1 conv) instead of one 1x1 conv per source resolution")
     ap.add_argument("--unfused-mlps", action="store_true", help="A/B: MAR's per-bin MLPs as four fdn_conv1x1 launches per block instead of one fdn_spectral_mlp2")
-    ap.add_argument("--cpu-720p", action="store_true", help="cpu_baseline also times ONE real 736 x 1280 oracle forward (BASELINE.md 4.3 'single timed run at "
-                    "720p': minutes of host time, off by default; the committed line is profiles/r05_cpu_720p.json)")
+    ap.add_argument("--cpu-720p", action="store_true", help="with --full: cpu_baseline also times ONE real 736 x 1280 oracle forward at any shape (BASELINE.md 4.3 "
+                    "'single timed run at 720p': minutes of host time; at the headline shape --full does it anyway)")
     ap.add_argument("--fdsa-full", action="store_true", help="A/B: route the level-1 FDSA sub-blocks through fdn_fdsa_full (one launch) instead of "
                     "fdn_fdsa_fused + fdn_fdsa_out (DESIGN.md section 4: built, correct, not the default)")
     ap.add_argument("--fdsa-pair", action="store_true", help="A/B: the FDSA sub-blocks of levels 1-2 as fdn_fdsa_fused + fdn_fdsa_out (two launches, the 4E-plane hand-off "
                     "through HBM: the round-5 route) instead of fdn_fdsa_fused_tail")
     ap.add_argument("--tail-pin-l2", action="store_true", help="A/B: the level-2 FDFFN project_in (64 -> 172) inside fdn_fdsa_fused_tail as well (default: level 1 only; measured slower at step level)")
     ap.add_argument("--no-tail-pin", action="store_true", help="A/B: the FDFFN project_in of level 1 as its own fdn_conv1x1 launch instead of inside fdn_fdsa_fused_tail")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short side measurements of BASELINE.json configs[2] (1080p B = 4 bf16 storage) "
-                    "and configs[4] (LPNet alone) that the default headline run appends as `other_configs`")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the replay of the timed graph on the configs[1] fixture frame (`parity` in the JSON line)")
-    ap.add_argument("--no-cpu-720p", action="store_true", help="cpu_baseline without the ONE real 736 x 1280 oracle forward (~3 minutes of host time) that the "
-                    "default headline run includes")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline figure does not need: roofline / top_kernels, cpu_baseline, "
+                         "parity, other_configs, and without_collectives when the scatter / gather is timed (minutes: see the module docstring)")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the short side measurements of BASELINE.json configs[2] (1080p B = 4 bf16 "
+                    "storage) and configs[4] (LPNet alone) that it appends as `other_configs` at the headline shape")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the replay of the timed graph on the configs[1] fixture frame (`parity` in the JSON line)")
+    ap.add_argument("--no-cpu-720p", action="store_true", help="with --full: cpu_baseline without the ONE real 736 x 1280 oracle forward (~3 minutes of host time) "
+                    "that it includes at the headline shape")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip roofline / top_kernels")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU / gloo rehearsal of the launcher, sharding, scatter / gather and timing protocol with a stand-in "
                          "forward (tests/test_multirank_cpu.py); measures nothing")
@@ -699,6 +707,8 @@ def main():
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    if a.cpu_720p and not a.full:
+        ap.error("--cpu-720p is part of the CPU baseline, which only --full measures")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(launch_ranks(a.gpus, sys.argv[1:]))       # parent: no GPU call before or after this line
@@ -843,14 +853,14 @@ def main():
         dumped = dump_outputs({"ratio" if a.config == "lpnet" else "result": out}, a.dump_outputs)
     host_issue_ms = host_s[0] / a.steps * 1e3
     dt_nosg = None
-    if sg:                                                             # beside it: the same K steps without the collectives
+    if sg and a.full:                                                  # beside it: the same K steps without the collectives
         dt_nosg = timed(False, a.steps)
     if a.dry_run and sg and rank == 0:                                 # the rehearsal also checks the plumbing
         ok = all(torch.equal(o, forward(i)) for o, i in zip(root_out, root_in))
         assert ok, "dry run: gathered outputs differ from the root's own forward"
 
     parity = None
-    if (rank == 0 and not a.dry_run and a.graph and a.config == "fdn" and a.variant == "lolblur" and a.dtype == "f32" and a.streams == 1
+    if (a.full and rank == 0 and not a.dry_run and a.graph and a.config == "fdn" and a.variant == "lolblur" and a.dtype == "f32" and a.streams == 1
             and (a.height, a.width) == (720, 1280) and not a.no_parity):
         parity = parity_against_reference(forward, x)
 
@@ -910,18 +920,18 @@ def main():
 
     roof = top = None
     prof = None
-    if rank == 0 and not a.no_roofline and not a.dry_run:
+    if a.full and rank == 0 and not a.no_roofline and not a.dry_run:
         roof, top, prof = roofline_of(x, a.dtype, (a.height, a.width), lpnet_only=a.config == "lpnet")
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not a.dry_run:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not a.dry_run:
         headline_default = (a.config == "fdn" and a.variant == "lolblur" and a.dtype == "f32" and (a.height, a.width, a.batch) == (720, 1280, 8))
         cpu = cpu_baseline(full_720p=a.cpu_720p or (headline_default and not a.no_cpu_720p))
 
     # BASELINE.json names two more single-GPU configurations: they are measured here, briefly, in the same process and by the same protocol (captured
-    # graph, untimed warm-up, K steps between synchronisations), so that every run of the headline command records them too (VERDICT r4, row g)
+    # graph, untimed warm-up, K steps between synchronisations), so that every --full run of the headline command records them too (VERDICT r4, row g)
     other = None
-    if (rank == 0 and world == 1 and not a.dry_run and not a.no_other_configs and a.config == "fdn" and a.variant == "lolblur" and a.graph
+    if (a.full and rank == 0 and world == 1 and not a.dry_run and not a.no_other_configs and a.config == "fdn" and a.variant == "lolblur" and a.graph
             and a.dtype == "f32" and (a.height, a.width, a.batch) == (720, 1280, 8) and not (a.fdsa_full or a.fdsa_pair or a.no_tail_pin or a.tail_pin_l2 or a.narrow_pipe or a.unfused_mlps or a.stats_launches or a.resample_upsample or a.aff_resized)):
         from fdn_hip.pipeline import GraphedStep
 

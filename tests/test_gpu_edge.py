@@ -258,12 +258,13 @@ def test_1080p_geometry_properties(A):
 # the N-GPU code path on one GPU, hipGraph replay
 # ---------------------------------------------------------------------------------------------------------------
 def test_bench_rccl_path_on_one_gpu(A):
-    """bench.py with the RCCL process group forced on (world size 1): scatter -> forward -> gather inside the timed loop."""
+    """bench.py with the RCCL process group forced on (world size 1): scatter -> forward -> gather inside the timed loop; with
+    --full the same steps without the collectives beside them."""
     env = dict(os.environ, FDN_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29641")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "3",
-                        "--height", "64", "--width", "96", "--scatter-gather", "--no-cpu-baseline", "--no-roofline"],
+                        "--height", "64", "--width", "96", "--scatter-gather", "--full", "--no-cpu-baseline", "--no-roofline"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -73,10 +73,11 @@ def test_shard_bounds():
 
 def test_bench_launcher_spawns_gpus_ranks():
     """`python bench.py --gpus 2` with no launcher around it must start 2 ranks itself (it used to run one rank
-    and print n_gpus 1), push the scatter / gather through the timed loop and report the collective world size."""
+    and print n_gpus 1), push the scatter / gather through the timed loop and report the collective world size; with --full
+    (which every rank receives) the same steps without the collectives as well."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run",
-                        "--batch", "3"], env=env, capture_output=True, text=True, timeout=300)
+                        "--batch", "3", "--full"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["rccl_ranks"] == 2 and line["config"]["global_batch"] == 6
@@ -88,6 +89,15 @@ def test_bench_rejects_world_size_mismatch():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--dry-run"], env=env, capture_output=True,
                        text=True, timeout=120)
     assert r.returncode != 0 and "must agree" in (r.stderr + r.stdout)
+
+
+def test_bench_cpu_720p_needs_full():
+    """--cpu-720p extends the CPU baseline, which only --full measures: asked for without it, the run refuses instead of silently
+    doing nothing."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cpu-720p", "--dry-run"], env=env, capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode != 0 and "--full" in r.stderr
 
 
 def test_bench_dump_outputs_dry_run(tmp_path):
@@ -133,13 +143,14 @@ def test_dump_outputs_fixed_sample_within_the_limit(tmp_path):
 
 def test_bench_launcher_world_8_with_affinity():
     """The configs[3] launch shape on the CPU: 8 ranks, each pinned to its own cut of the host cores before any GPU call, the
-    scatter / gather of a global batch of 8 x B through the timed loop (gloo)."""
+    scatter / gather of a global batch of 8 x B through the timed loop (gloo).  A plain run times nothing but those steps."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--dry-run",
                         "--batch", "2"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 8 and line["config"]["rccl_ranks"] == 8 and line["config"]["global_batch"] == 16
+    assert "without_collectives" not in line
     aff = line["config"]["cpu_affinity_rank0"]
     assert aff is not None and aff["cores"] >= 1 and aff["cores"] <= max(1, (os.cpu_count() or 8) // 8 + 1)
     assert line["config"]["host_issue_ms_per_step"] >= 0.0
