@@ -10,6 +10,10 @@ Mirrors what inference_fdn_lolblur.py:47-75 does on the host with cv2 / numpy:
 
 here as two HIP kernels (fdn_pre_u8 / fdn_post_u8) around the drop-in modules, batched: B images of one size go
 through one forward.  No CPU fallback: the uint8 tensors must live on the ROCm device.
+
+validate_u8 is the same walk with a ground truth beside the input, as the reference's validation does it
+(basicsr/models/image_restoration_model.py:578-586, :650-658, :746-748, :844-848): the ratio from the ground truth (gt_ratio), and
+PSNR / SSIM of the uint8 result against the uint8 ground truth.
 """
 import ctypes
 import torch
@@ -61,10 +65,26 @@ def lolv1_ratio(x, lp_ratio):
     """inference_fdn_lolv1.py:57-61: ratio_i = mean(Grayscale(padded input)) / LPNet(padded input).  The plane means
     come from fdn_global_avgpool; Grayscale is linear (0.2989 R + 0.587 G + 0.114 B), so its mean is the same
     combination of the three plane means ([B,3] values, combined on the device)."""
+    return _gray_mean(x) / lp_ratio
+
+
+def _gray_mean(x):
+    """[B,3,H,W] R, G, B -> [B,1]: the mean of transforms.Grayscale's plane"""
     from . import ops
     m = ops.global_avgpool(x).reshape(x.shape[0], 3)
-    gray = 0.2989 * m[:, 0:1] + 0.587 * m[:, 1:2] + 0.114 * m[:, 2:3]
-    return gray / lp_ratio
+    return 0.2989 * m[:, 0:1] + 0.587 * m[:, 1:2] + 0.114 * m[:, 2:3]
+
+
+def gt_ratio(x_lq, x_gt):
+    """The ratio the reference's validation feeds FDN (image_restoration_model.py:650-654 with use_ratio, options/train/FDN.yml):
+    mean(Grayscale(padded input)) / mean(Grayscale(padded ground truth)), both reflect-padded as :583-586 -> [B,1].  Built like
+    lolv1_ratio on fdn_global_avgpool.  A ground truth whose gray mean is 0 has no ratio."""
+    if x_lq.shape != x_gt.shape or x_lq.dim() != 4 or x_lq.shape[1] != 3:
+        raise FdnHipError(f"gt_ratio needs two [B,3,H,W] tensors of one shape, got {tuple(x_lq.shape)} and {tuple(x_gt.shape)}")
+    high = _gray_mean(x_gt)
+    if bool((high == 0).any()):
+        raise FdnHipError("gt_ratio: a ground-truth image has gray mean 0")
+    return _gray_mean(x_lq) / high
 
 
 @torch.no_grad()
@@ -87,3 +107,35 @@ def enhance_u8(net, lpnet, img_u8, bgr=True, ratio_mode="lolblur", ratio=None):
         ratio = lolv1_ratio(x, lpnet(x))
         result = net(x, ratio_i=ratio, device=x.device)[0]
     return postprocess(result.contiguous(), h, w, bgr=bgr)
+
+
+@torch.no_grad()
+def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=True):
+    """One validation step of the reference (image_restoration_model.py:578-586, :650-658, :746-748, :844-848) for a batch, on the device:
+    uint8 low-quality and ground-truth frames [B,h,w,3] -> (uint8 result [B,h,w,3], PSNR list, SSIM list, ratio [B,1]).
+    ratio_mode: "gt" feeds mean(gray(lq)) / mean(gray(gt)) as the validation does (gt_ratio; lpnet is not used and may be None),
+    "lolblur" / "lolv1" feed LPNet's ratio as enhance_u8 does.  The scores are calculate_psnr / calculate_ssim of the uint8 result
+    (img1) against gt_u8, as the reference scores tensor2img's images (fdn_hip.metrics.calculate_psnr_ssim_u8).  Eager forward on the
+    caller's stream."""
+    from .metrics import calculate_psnr_ssim_u8
+    if ratio_mode not in ("gt", "lolblur", "lolv1"):
+        raise ValueError(f"ratio_mode {ratio_mode!r}")
+    if ratio_mode != "gt" and lpnet is None:
+        raise FdnHipError(f"ratio_mode {ratio_mode!r} needs lpnet")
+    if lq_u8.dim() == 3:
+        lq_u8 = lq_u8.unsqueeze(0)
+    if gt_u8.dim() == 3:
+        gt_u8 = gt_u8.unsqueeze(0)
+    if lq_u8.shape != gt_u8.shape:
+        raise FdnHipError(f"Image shapes are different: {tuple(lq_u8.shape)}, {tuple(gt_u8.shape)}.")
+    x, h, w = preprocess(lq_u8, bgr=bgr)
+    if ratio_mode == "gt":
+        ratio = gt_ratio(x, preprocess(gt_u8, bgr=bgr)[0])
+    elif ratio_mode == "lolblur":
+        ratio = lpnet(x)
+    else:
+        ratio = lolv1_ratio(x, lpnet(x))
+    ratio = ratio.contiguous()
+    out = postprocess(net(x, ratio_i=ratio, device=x.device)[0].contiguous(), h, w, bgr=bgr)
+    psnr, ssim = calculate_psnr_ssim_u8(out, gt_u8, crop_border=crop_border, bgr=bgr)
+    return out, psnr, ssim, ratio

@@ -4,6 +4,9 @@
 ROCm tensors.  With `test_y_channel` the channels must be in B, G, R order and the range [0, 255], as the reference's callers pass
 them (`tensor2img(..., rgb2bgr=True)`).  No CPU fallback.
 
+`calculate_psnr_ssim_u8` scores batches of 8-bit images, what the reference's validation (image_restoration_model.py:746-748, :844-848)
+and scripts/metrics/calculate_psnr_ssim.py do: the default branch in two launches over the uint8 batch (csrc/metrics_pair.hip).
+
 The same package's no-reference metric, `calculate_niqe` (basicsr/metrics/niqe.py:67-205), is here too: the plane, the MSCN planes
 and the per-block features on the GPU (csrc/niqe.hip), the 36-feature MVG fit on the host in float64 with the reference's own calls.
 
@@ -89,6 +92,102 @@ def calculate_ssim(img1, img2, crop_border=0, test_y_channel=False, ssim3d=True)
     acc = torch.zeros(1, dtype=torch.float64, device=a.device)
     check(lib().fdn_ssim3d(_ptr(a), _ptr(b), C, H, W, ctypes.c_float(max_value), _ptr(ws), _ptr(acc), stream()), "fdn_ssim3d")
     return float(acc.item()) / a.numel()
+
+
+# ---- paired validation on batches of 8-bit images (image_restoration_model.py:746-748, :844-848; scripts/metrics/calculate_psnr_ssim.py) --
+PAIR_PARTS = 256                                          # FDN_PAIR_PARTS of include/fdn_hip.h: int64 partial pairs per image of fdn_pair_sse_u8
+
+
+def ssim3d_taps():
+    """cv2.getGaussianKernel(11, 1.5), float64 [11]: exp(-(i - 5)^2 / (2 sigma^2)) normalised (psnr_ssim.py:153-156)"""
+    i = np.arange(11, dtype=np.float64) - 5.0
+    k = np.exp(-(i * i) / (2.0 * 1.5 * 1.5))
+    return k / k.sum()
+
+
+def ssim3d_channel_matrix():
+    """The channel pass of the 11 x 11 x 11 window over a 3-channel image with replicate padding (:158), float64 [c_out][c_in]: tap t of
+    output channel c reads channel clamp(c + t - 5, 0, 2), so the pass is this 3 x 3 matrix of tap sums."""
+    k, m = ssim3d_taps(), np.zeros((3, 3))
+    for co in range(3):
+        for t in range(11):
+            m[co, min(max(co + t - 5, 0), 2)] += k[t]
+    return m
+
+
+def _u8_pair(img1, img2, crop_border):
+    """-> (a, b, single): two contiguous uint8 [B][h][w][3] tensors on one ROCm device"""
+    s1, s2 = tuple(getattr(img1, "shape", ())), tuple(getattr(img2, "shape", ()))
+    if s1 != s2:
+        raise FdnHipError(f"Image shapes are different: {s1}, {s2}.")                                # psnr_ssim.py:30
+    out = []
+    for img in (img1, img2):
+        if isinstance(img, np.ndarray):
+            img = torch.from_numpy(np.ascontiguousarray(img))
+        if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or img.dim() not in (3, 4) or img.shape[-1] != 3:
+            raise FdnHipError("calculate_psnr_ssim_u8 takes uint8 images (h,w,3) or (B,h,w,3), numpy arrays or tensors, got "
+                              f"{getattr(img, 'dtype', type(img).__name__)} {tuple(getattr(img, 'shape', ()))}")
+        out.append(img if img.dim() == 4 else img.unsqueeze(0))
+    cb = int(crop_border)
+    B, h, w, _ = out[0].shape
+    if cb < 0:
+        raise FdnHipError("crop_border must be >= 0")
+    if B < 1 or h <= 2 * cb or w <= 2 * cb:
+        raise FdnHipError(f"calculate_psnr_ssim_u8: nothing is left of {B} image(s) of {h}x{w} with crop_border={cb}")
+    devs = {t.device for t in out if t.is_cuda}
+    if len(devs) > 1:
+        raise FdnHipError(f"calculate_psnr_ssim_u8: the two images are on different devices ({out[0].device}, {out[1].device})")
+    dev = next(iter(devs), None)
+    if dev is None:
+        if not torch.cuda.is_available():
+            raise FdnHipError("calculate_psnr_ssim_u8 needs a ROCm device; there is no CPU fallback")
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return out[0].to(dev).contiguous(), out[1].to(dev).contiguous(), len(s1) == 3
+
+
+def _psnr_from_sse(sse, mx, n):
+    mse = sse / n                                                                                      # :59 (integers: exact)
+    if mse == 0:
+        return float("inf")                                                                            # :60-61
+    return 20.0 * math.log10((1.0 if mx <= 1 else 255.0) / math.sqrt(mse))                              # :62-63
+
+
+def calculate_psnr_ssim_u8(img1, img2, crop_border=0, test_y_channel=False, ssim3d=True, bgr=True):
+    """calculate_psnr and calculate_ssim (psnr_ssim.py:8-70, :243-329) of 8-bit image pairs, as the reference's validation and its
+    scripts/metrics/calculate_psnr_ssim.py score them: (h,w,3) or (B,h,w,3) uint8 numpy arrays or tensors (host data is moved to the
+    current ROCm device).  img1 decides the peak value (img1.max() <= 1 -> 1, else 255).  -> (psnr, ssim): two floats for one pair, two
+    lists of B floats for a batch.  The default branch (RGB PSNR, 3-D SSIM) is two kernels over the whole batch and one device-to-host
+    copy; the scores are bit-identical across calls and do not depend on the rest of the batch.  test_y_channel=True and ssim3d=False
+    go image by image through the float32 entry points (calculate_psnr / calculate_ssim above).  bgr says whether the channels are
+    B, G, R (cv2.imread, tensor2img) or R, G, B; only the Y channel depends on it (the 3-D window is symmetric along the channel axis)."""
+    a, b, single = _u8_pair(img1, img2, crop_border)
+    cb = int(crop_border)
+    B, h, w, _ = a.shape
+    if test_y_channel or not ssim3d:
+        psnr, ssim = [], []
+        for i in range(B):
+            x, y = (t[i].permute(2, 0, 1).to(torch.float32) for t in (a, b))                           # (3,h,w) planes, values 0..255
+            if test_y_channel and not bgr:
+                x, y = x.flip(0), y.flip(0)
+            psnr.append(calculate_psnr(x, y, cb, test_y_channel))
+            ssim.append(calculate_ssim(x, y, cb, test_y_channel, ssim3d))
+    else:
+        l = lib()
+        nws = int(l.fdn_pair_ssim3d_ws(B, h, w, cb))
+        stats = torch.empty((B, PAIR_PARTS, 2), dtype=torch.int64, device=a.device)
+        ws = torch.empty(max(nws, 1), dtype=torch.float64, device=a.device)
+        out = torch.empty((B, 3), dtype=torch.float64, device=a.device)
+        taps, mix = ssim3d_taps(), np.ascontiguousarray(ssim3d_channel_matrix())
+        with torch.cuda.device(a.device):
+            s = stream()
+            check(l.fdn_pair_sse_u8(_ptr(a), _ptr(b), B, h, w, cb, _ptr(stats), s), "fdn_pair_sse_u8")
+            check(l.fdn_pair_ssim3d_u8(_ptr(a), _ptr(b), B, h, w, cb, _ptr(stats), taps.ctypes.data_as(ctypes.c_void_p),
+                                       mix.ctypes.data_as(ctypes.c_void_p), _ptr(ws), _ptr(out), s), "fdn_pair_ssim3d_u8")
+        res = out.cpu().tolist()                                                                       # the one copy: [B][sse, max, ssim]
+        n = 3 * (h - 2 * cb) * (w - 2 * cb)
+        psnr = [_psnr_from_sse(int(r[0]), r[1], n) for r in res]
+        ssim = [r[2] for r in res]
+    return (psnr[0], ssim[0]) if single else (psnr, ssim)
 
 
 # ---- NIQE (basicsr/metrics/niqe.py) ------------------------------------------------------------------------------------------------------

@@ -1,0 +1,123 @@
+"""Paired evaluation on the HIP path: inference and scoring in one pass, the role of the reference's validation
+(basicsr/models/image_restoration_model.py:564-711, :713-893 with options/train/FDN.yml: the ground-truth ratio, tensor2img, then
+calculate_psnr / calculate_ssim on the 8-bit images), without the training framework around it:
+
+    decode (PIL, worker threads) -> uint8 on the GPU -> fdn_pre_u8 -> ratio -> FDN -> fdn_post_u8 -> PSNR / SSIM against the ground truth
+
+--ratio gt feeds FDN mean(gray(lq)) / mean(gray(gt)) as the validation does (:650-654; no LPNet needed), --ratio lpnet the ratio the
+inference drivers feed (LPNet's prediction for --variant lolblur, mean(gray) / prediction for lolv1).  --lq and --gt are globs, sorted
+and paired by index; frames of equal size are batched and decoded one batch ahead.  The frames leave the GPU only with --output; the
+scores take one small copy per batch.  Needs a ROCm GPU and the built libfdn_hip.so; there is no CPU fallback.
+
+    python validate_fdn.py --fdn FDN_lolblur.pth --lq 'lolblur/test/low_blur/*/*' --gt 'lolblur/test/high_sharp_scaled/*/*' --csv scores.csv
+"""
+import argparse
+import glob
+import os
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from calculate_psnr_ssim import decoded_groups  # noqa: E402
+
+RATIO_MODE = {("gt", "lolblur"): "gt", ("gt", "lolv1"): "gt", ("lpnet", "lolblur"): "lolblur", ("lpnet", "lolv1"): "lolv1"}
+
+
+def pair_frames(lq_glob, gt_glob):
+    """sorted(glob(lq)) and sorted(glob(gt)), paired by index -> [(lq, gt)]"""
+    lq, gt = sorted(glob.glob(lq_glob)), sorted(glob.glob(gt_glob))
+    if not lq:
+        raise ValueError(f"no input frames match {lq_glob!r}")
+    if len(lq) != len(gt):
+        raise ValueError(f"{len(lq)} input frames ({lq_glob!r}) but {len(gt)} ground-truth frames ({gt_glob!r})")
+    return list(zip(lq, gt))
+
+
+def output_paths(lq_paths, output):
+    """a frame <common parent>/0256/0089.png is written to <output>/0256/0089.png, as the inference drivers keep the sequence folders"""
+    root = os.path.commonpath([os.path.dirname(os.path.abspath(p)) for p in lq_paths])
+    dest = [os.path.join(output, os.path.relpath(os.path.abspath(p), root)) for p in lq_paths]
+    if len(set(dest)) != len(dest):
+        raise ValueError("two input frames map to the same output path")
+    return dest
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--fdn", required=True, help="FDN checkpoint ({'params': state_dict})")
+    ap.add_argument("--lpnet", default=None, help="LPNet checkpoint; needed with --ratio lpnet only")
+    ap.add_argument("--lq", required=True, help="low-quality input frames: a glob, sorted")
+    ap.add_argument("--gt", required=True, help="ground-truth frames: a glob, sorted and paired with --lq by index")
+    ap.add_argument("--variant", choices=("lolblur", "lolv1"), default="lolblur", help="FDN (dim 32) or FDN_lolv1 (dim 24)")
+    ap.add_argument("--ratio", choices=("gt", "lpnet"), default="gt", help="where ratio_i comes from: the ground truth (validation) or LPNet")
+    ap.add_argument("--crop_border", type=int, default=0, help="pixels cut from every edge before scoring")
+    ap.add_argument("--output", default=None, help="directory for the restored frames; without it no frame is written")
+    ap.add_argument("--csv", default=None, help="file for one 'frame,psnr,ssim,ratio' line per pair")
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    if a.ratio == "lpnet" and not a.lpnet:
+        ap.error("--ratio lpnet needs --lpnet")
+    if a.crop_border < 0:
+        ap.error("--crop_border must be >= 0")
+    try:
+        a.pairs = pair_frames(a.lq, a.gt)
+        a.dest = output_paths([p for p, _ in a.pairs], a.output) if a.output else None
+    except ValueError as e:
+        ap.error(str(e))
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    import torch
+    from fdn_hip.harness import validate_u8
+    from inference_fdn_lolblur import load_params, write_rgb
+    from basicsr.models.archs.LPNet_arch import I_predict_net
+    if a.variant == "lolblur":
+        from basicsr.models.archs.FDN_arch import FDN as Net
+    else:
+        from basicsr.models.archs.fdnlol24_arch import FDN_lolv1 as Net
+
+    dev = torch.device(a.device)
+    torch.cuda.set_device(dev)
+    net = Net().to(dev).eval()
+    net.load_state_dict(load_params(a.fdn), strict=True)
+    lp = None
+    if a.ratio == "lpnet":
+        lp = I_predict_net().to(dev).eval()
+        lp.load_state_dict(load_params(a.lpnet), strict=True)
+    mode = RATIO_MODE[(a.ratio, a.variant)]
+
+    n = len(a.pairs)
+    psnr, ssim, ratio = [None] * n, [None] * n, [None] * n
+    with ThreadPoolExecutor(max_workers=4) as pool:
+        writers = []
+        for idx, lqs, gts in decoded_groups(a.pairs, a.batch, pool):
+            lq, gt = torch.from_numpy(lqs).to(dev), torch.from_numpy(gts).to(dev)
+            out, p, s, r = validate_u8(net, lp, lq, gt, ratio_mode=mode, crop_border=a.crop_border, bgr=False)
+            r = r.reshape(-1).cpu().tolist()
+            frames = out.cpu().numpy() if a.dest else None
+            for k, i in enumerate(idx):
+                psnr[i], ssim[i], ratio[i] = p[k], s[k], r[k]
+                if a.dest:
+                    writers.append(pool.submit(write_rgb, a.dest[i], frames[k]))
+        for w in writers:
+            w.result()
+    for i, (lq_path, _) in enumerate(a.pairs):
+        basename = os.path.splitext(os.path.basename(lq_path))[0]
+        print(f'{i+1:3d}: {basename:25}. \tPSNR: {psnr[i]:.6f} dB, \tSSIM: {ssim[i]:.6f}')
+    print(f'Average: PSNR: {sum(psnr) / n:.6f} dB, SSIM: {sum(ssim) / n:.6f}')
+    if a.csv:
+        os.makedirs(os.path.dirname(a.csv) or ".", exist_ok=True)
+        with open(a.csv, "w") as f:
+            f.write("frame,psnr,ssim,ratio\n")
+            for (lq_path, _), p, s, r in zip(a.pairs, psnr, ssim, ratio):
+                f.write(f"{lq_path},{p!r},{s!r},{r!r}\n")
+    if a.dest:
+        print(f"{n} frames -> {a.output}")
+
+
+if __name__ == "__main__":
+    main()

@@ -36,7 +36,7 @@ enum { FDN_PRO_NONE = 0, FDN_PRO_LN = 1, FDN_PRO_LN3_GATE = 2, FDN_PRO_LN_MULADD
 enum { FDN_EPI_NONE = 0, FDN_EPI_RES = 1, FDN_EPI_MULADD = 2 };
 enum { FDN_RS_BILINEAR_HALF = 0, FDN_RS_BILINEAR_X2 = 1, FDN_RS_NEAREST_HALF = 2, FDN_RS_NEAREST_X2 = 3, FDN_RS_PIXEL_UNSHUFFLE = 4 };
 
-/* library version / build info: returns the ABI version (bumped on any signature change; 19 since the fdn_lpips_* entry points and fdn_maxpool2d) */
+/* library version / build info: returns the ABI version (bumped on any signature change; 20 since the fdn_pair_* entry points) */
 int fdn_abi_version(void);
 const char* fdn_error_string(int code);
 /* Diagnostic switch, process-wide, default 0 = every matrix product that has a split-bf16 form runs on the bf16 matrix pipe
@@ -429,6 +429,26 @@ int fdn_lpips_prep_f32(const float* x, float* out, int B, int H, int W, int from
 int fdn_maxpool2d(const float* x, float* out, long planes, int H, int W, int k, int s, fdn_stream_t stream);
 int fdn_lpips_layer(const float* f, const float* w, double* out, int B, int C, int H, int W, int accumulate, double* ws,
                     fdn_stream_t stream);
+/* ABI 20.  Paired validation on batches of 8-bit images: what the reference's validation scores after tensor2img
+ * (basicsr/models/image_restoration_model.py:746-748, :844-848) and what scripts/metrics/calculate_psnr_ssim.py scores, in the default
+ * branch of calculate_psnr / calculate_ssim (RGB, ssim3d=True).  a (img1) and b (img2): uint8 [B][h][w][3] as fdn_post_u8 writes them;
+ * crop = crop_border, cut from every edge before anything else (psnr_ssim.py:50-52, :295-297); h, w > 2 crop.  No atomics and no
+ * caller-zeroed memory: every sum is folded in a fixed order, so a score is bit-identical across calls and does not depend on the
+ * other images of the batch.  All launches on `stream`.
+ * fdn_pair_sse_u8: replaces np.mean((img1 - img2)**2) and img1.max() (:59-62).  stats [B][FDN_PAIR_PARTS][2] int64: part p of image b
+ *   holds the sum of squared differences ([0]) and the maximum of a ([1]) over the cropped rows p, p + FDN_PAIR_PARTS, ...; integers,
+ *   so their total is exact.
+ * fdn_pair_ssim3d_u8: replaces _ssim_3d (:163-200) with its max_value (:311) and C1, C2 (:176-177) taken from `stats` on the device.
+ *   One tiled launch works on the bytes of the two images (each tile loads its apron channel by channel) and evaluates the map: the 11 x 11 x 11 window as a W pass, an H pass (taps11 = HOST pointer to
+ *   getGaussianKernel(11, 1.5), float64) and the 3 x 3 channel matrix the replicate-padded channel pass collapses to (chmix9 = HOST
+ *   pointer, float64 row-major [c_out][c_in]), all in fp32.  ws: fdn_pair_ssim3d_ws(B, h, w, crop) doubles (one per tile; 0 = bad
+ *   arguments).  A second launch folds everything: out3 [B][3] float64 = {sum of squared differences, max of a, mean of the SSIM map},
+ *   the one array the host needs for PSNR (:59-63) and SSIM. */
+enum { FDN_PAIR_PARTS = 256 };
+long fdn_pair_ssim3d_ws(int B, int h, int w, int crop);
+int fdn_pair_sse_u8(const unsigned char* a, const unsigned char* b, int B, int h, int w, int crop, long* stats, fdn_stream_t stream);
+int fdn_pair_ssim3d_u8(const unsigned char* a, const unsigned char* b, int B, int h, int w, int crop, const long* stats,
+                       const double* taps11, const double* chmix9, double* ws, double* out3, fdn_stream_t stream);
 
 #ifdef __cplusplus
 }
