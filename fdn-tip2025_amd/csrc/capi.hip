@@ -72,6 +72,20 @@ bool fdn_occupancy(int* blocks_per_cu, const void* kernel, int threads, size_t l
     return true;
 }
 
+int fdn_persistent_grid(const void* kernel, int threads, size_t lds, int total_tiles, fdn_grid_cap cap) {
+    const int cus = fdn_device_cus();
+    if (cus <= 0) return -1;
+    if (lds > 48 * 1024 && !fdn_allow_dynamic_lds(kernel, lds)) return -1;
+    int per_cu = 1 << 20;
+    if (cap.by_occupancy && !fdn_occupancy(&per_cu, kernel, threads, lds)) per_cu = 1;
+    if (cap.max_wg > 0 && per_cu > cap.max_wg) per_cu = cap.max_wg;
+    if (cap.max_waves > 0 && per_cu * (threads / 64) > cap.max_waves) per_cu = cap.max_waves / (threads / 64);
+    if (cap.lds_budget > 0 && lds > 0 && (size_t)per_cu > cap.lds_budget / lds) per_cu = (int)(cap.lds_budget / lds);
+    if (per_cu < 1) per_cu = 1;
+    const long grid = (long)cus * per_cu;
+    return grid > total_tiles ? total_tiles : (int)grid;
+}
+
 namespace {
 int device_cus_locked(int dev) {                                  // g_mu held
     if (g_cus_by_dev[dev] == 0) {

@@ -25,7 +25,20 @@ bool fdn_allow_dynamic_lds(const void* kernel, size_t bytes);
 bool fdn_matrix_pipe_f32();                                   // fdn_set_matrix_pipe(1): no bf16-MFMA kernel is launched
 void fdn_note_bf16_launch();                                  // called by every launcher of a bf16-MFMA kernel (fdn_bf16_mfma_launches)
 bool fdn_matrix_pipe_wide();                                  // default mode: fdn_fdsa_out's level-2 shape on the bf16 pipe too (mode 2 = the ABI-10 default keeps it on fp32 MFMAs)
-bool fdn_occupancy(int* blocks_per_cu, const void* kernel, int threads, size_t lds);   // hipOccupancyMaxActiveBlocksPerMultiprocessor, cached
+bool fdn_occupancy(int* blocks_per_cu, const void* kernel, int threads, size_t lds);   // the runtime's occupancy query, cached
+// The grid of a persistent kernel: min(CUs * workgroups per CU, total_tiles), or < 0 (no device, or the dynamic-LDS limit - raised here when
+// lds > 48 KB - is refused): the caller returns FDN_ERR_LAUNCH.  Workgroups per CU start from the cached occupancy (by_occupancy; 1 when the query
+// fails) or unbounded, then every cap that is set (> 0) applies: max_wg, max_waves / (threads / 64), lds_budget / lds; at least 1.
+struct fdn_grid_cap {
+    bool by_occupancy;
+    int max_wg, max_waves;
+    size_t lds_budget;
+};
+int fdn_persistent_grid(const void* kernel, int threads, size_t lds, int total_tiles, fdn_grid_cap cap);
+template <typename K>
+int fdn_persistent_grid(K kernel, int threads, size_t lds, int total_tiles, fdn_grid_cap cap) {
+    return fdn_persistent_grid(reinterpret_cast<const void*>(kernel), threads, lds, total_tiles, cap);
+}
 
 // Y of ITU-R BT.601 of one B, G, R pixel in [0, 255], the reference's to_y_channel (metric_util.py:34-47 -> matlab_functions.py:207-238,
 // y_only): float32 / 255, float64 dot with (24.966, 128.553, 65.481) + 16, / 255 and back to float32, * 255 in float32 - the reference's
@@ -142,6 +155,13 @@ __device__ __forceinline__ float2 cmulc(float2 a, float2 b) {  // a * conj(b)
 }
 __device__ __forceinline__ float cabs2(float2 a) { return sqrtf(a.x * a.x + a.y * a.y); }
 
+// Per-pixel LayerNorm helpers of the two FDSA tails (fdsa_out.hip, fdsa_tail.hpp), for one pixel and for a pair: the sum over the two lane
+// halves of an MFMA result, and 1 / sqrt(var + eps).
+__device__ __forceinline__ float xsum32(float v) { return v + __shfl_xor(v, 32); }
+__device__ __forceinline__ fdn_f32x2 xsum32(fdn_f32x2 v) { return fdn_f32x2{v.x + __shfl_xor(v.x, 32), v.y + __shfl_xor(v.y, 32)}; }
+__device__ __forceinline__ float rsqrt_eps(float v) { return 1.0f / sqrtf(v + 1e-5f); }
+__device__ __forceinline__ fdn_f32x2 rsqrt_eps(fdn_f32x2 v) { return fdn_f32x2{1.0f / sqrtf(v.x + 1e-5f), 1.0f / sqrtf(v.y + 1e-5f)}; }
+
 // Workgroup -> work item for tiled kernels.  The dispatcher deals workgroups round-robin over the 8 XCDs (blocks b and b + 8
 // share one, MI355X_MICROARCH.md), so with the natural order horizontally adjacent tiles of a plane land on different XCDs and
 // the 128-byte lines both touch (a halo row of 64 + 2 floats spans 4 lines, 2 of them shared) are fetched from the fabric twice:
@@ -179,54 +199,52 @@ __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
     const bf2 v = {(__bf16)lo, (__bf16)hi};
     return __builtin_bit_cast(unsigned, v);
 }
-// element loads / stores through a raw buffer resource; `voff` / `soff` are BYTE offsets of the storage type
+#include "buffer_io.hpp"
+// element loads / stores of the storage type through a raw buffer resource; `voff` / `soff` are BYTE offsets of the storage type
 template <bool BF>
-__device__ __forceinline__ float st_load1(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
+__device__ __forceinline__ float st_load1(rsrc_t r, unsigned voff, unsigned soff) {
     if constexpr (BF) return __uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, 0) << 16);
-    else return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
+    else return bload(r, voff, soff);
 }
 template <bool BF>
-__device__ __forceinline__ void st_store1(float v, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
+__device__ __forceinline__ void st_store1(float v, rsrc_t r, unsigned voff, unsigned soff) {
     if constexpr (BF) __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(pack_bf16(v, 0.f) & 0xFFFFu), r, voff, soff, 0);
-    else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, soff, 0);
+    else bstore(v, r, voff, soff);
 }
 template <bool BF>
-__device__ __forceinline__ void st_load2(float (&v)[2], __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
+__device__ __forceinline__ void st_load2(float (&v)[2], rsrc_t r, unsigned voff, unsigned soff) {
     if constexpr (BF) {
         const unsigned u = __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0);
         v[0] = bf16_lo(u);
         v[1] = bf16_hi(u);
     } else {
-        const fdn_u32x2 u = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
-        v[0] = __uint_as_float(u.x);
-        v[1] = __uint_as_float(u.y);
+        const fdn_f32x2 f = bload2(r, voff, soff);
+        v[0] = f.x;
+        v[1] = f.y;
     }
 }
 template <bool BF>
-__device__ __forceinline__ void st_store2(const float (&v)[2], __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
+__device__ __forceinline__ void st_store2(const float (&v)[2], rsrc_t r, unsigned voff, unsigned soff) {
     if constexpr (BF) __builtin_amdgcn_raw_buffer_store_b32(pack_bf16(v[0], v[1]), r, voff, soff, 0);
-    else __builtin_amdgcn_raw_buffer_store_b64(fdn_u32x2{__float_as_uint(v[0]), __float_as_uint(v[1])}, r, voff, soff, 0);
+    else bstore2(fdn_f32x2{v[0], v[1]}, r, voff, soff);
 }
 template <bool BF>
-__device__ __forceinline__ void st_load4(float (&v)[4], __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
+__device__ __forceinline__ void st_load4(float (&v)[4], rsrc_t r, unsigned voff, unsigned soff) {
     if constexpr (BF) {
         const fdn_u32x2 u = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
         v[0] = bf16_lo(u.x); v[1] = bf16_hi(u.x); v[2] = bf16_lo(u.y); v[3] = bf16_hi(u.y);
     } else {
-        const fdn_u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
-        v[0] = __uint_as_float(u.x); v[1] = __uint_as_float(u.y); v[2] = __uint_as_float(u.z); v[3] = __uint_as_float(u.w);
+        const fdn_f32x4 f = bload4(r, voff, soff);
+        v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
     }
 }
 template <bool BF>
-__device__ __forceinline__ void st_store8(const float (&v)[8], __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
+__device__ __forceinline__ void st_store8(const float (&v)[8], rsrc_t r, unsigned voff, unsigned soff) {
     if constexpr (BF) {
         __builtin_amdgcn_raw_buffer_store_b128(fdn_u32x4{pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]), pack_bf16(v[6], v[7])},
                                                r, voff, soff, 0);
     } else {
-        __builtin_amdgcn_raw_buffer_store_b128(fdn_u32x4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])},
-                                               r, voff, soff, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(fdn_u32x4{__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7])},
-                                               r, voff + 16u, soff, 0);
+        bstore8(v, r, voff, soff);
     }
 }
 template <bool BF> constexpr unsigned st_bytes() { return BF ? 2u : 4u; }

@@ -14,18 +14,7 @@
 namespace {
 
 constexpr int KC = 32;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-
-__device__ __forceinline__ rsrc_t mk_rsrc(const float* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ float bload(rsrc_t r, unsigned voff, unsigned soff) {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ void bstore(float v, rsrc_t r, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, soff, 0);
-}
+using f32x16 = fdn_f32x16;
 
 struct C3Args {
     const float* x; const float* w; const float* bias; const float* res; float* out;
@@ -369,17 +358,13 @@ int launch_split(const C3Args& a, hipStream_t s) {
 template <int MT, int NW>
 int launch(C3Args a, hipStream_t s) {
     const size_t lds = 2UL * KC * (MT * 32 + 1) * sizeof(float);
-    const int g_cus = fdn_device_cus();
-    if (g_cus <= 0) return FDN_ERR_LAUNCH;
     a.tiles_per_img = cdiv((long)a.H * a.W, NW * 32);
     a.total_tiles = a.B * a.tiles_per_img;
     // 4-wave workgroups, two (independent) per CU: their per-chunk barriers drift apart (as in gemm1x1.hip)
-    int per_cu = 0;
-    if (!fdn_occupancy(&per_cu, reinterpret_cast<const void*>(conv3x3_kernel<MT, NW>), NW * 64, lds) || per_cu < 1) per_cu = 1;
-    if (per_cu * NW > 16) per_cu = 16 / NW;
-    int grid = g_cus * per_cu;
-    if (grid > a.total_tiles) grid = a.total_tiles;
-    hipLaunchKernelGGL((conv3x3_kernel<MT, NW>), dim3(grid), dim3(NW * 64), lds, s, a);
+    auto kern = conv3x3_kernel<MT, NW>;
+    const int grid = fdn_persistent_grid(kern, NW * 64, lds, a.total_tiles, {true, 0, 16, 0});
+    if (grid < 0) return FDN_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, s, a);
     return fdn_launch_status();
 }
 

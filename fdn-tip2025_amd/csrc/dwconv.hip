@@ -54,23 +54,6 @@ __global__ __launch_bounds__(256) void dw3x3_kernel(const float* __restrict__ x,
 
 // buffer addressing: per-lane byte offsets are computed once (invalid lanes get an out-of-range offset, which
 // loads 0 and drops stores) and the channel plane is a scalar offset, so plane walks cost no vector ALU work
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-constexpr unsigned OOB = 0x80000000u;
-__device__ __forceinline__ rsrc_t mk_rsrc(const float* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ float bload(rsrc_t r, unsigned voff, unsigned soff) {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ void bstore(float v, rsrc_t r, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, soff, 0);
-}
-__device__ __forceinline__ float __attribute__((ext_vector_type(4))) bload4(rsrc_t r, unsigned voff, unsigned soff) {
-    typedef unsigned u4 __attribute__((ext_vector_type(4)));
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    const u4 u = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
-    return f4{__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w)};
-}
 constexpr int HALO = (TH + 2) * LW;
 constexpr int HPT = (HALO + 255) / 256;   // 9 halo elements per thread
 

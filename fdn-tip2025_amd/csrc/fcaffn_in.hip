@@ -18,32 +18,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-
-__device__ __forceinline__ rsrc_t mk_rsrc(const float* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)bytes, 0x00020000);
-}
-template <int VEC> struct VecT;
-template <> struct VecT<1> { typedef float type __attribute__((ext_vector_type(1))); };
-template <> struct VecT<2> { typedef float type __attribute__((ext_vector_type(2))); };
-template <int VEC>
-__device__ __forceinline__ typename VecT<VEC>::type bloadv(rsrc_t r, unsigned voff, unsigned soff) {
-    typename VecT<VEC>::type f;
-    if constexpr (VEC == 2) {
-        const fdn_u32x2 u = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
-        f[0] = __uint_as_float(u.x);
-        f[1] = __uint_as_float(u.y);
-    } else {
-        f[0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-    }
-    return f;
-}
-template <int VEC>
-__device__ __forceinline__ void bstorev(typename VecT<VEC>::type f, rsrc_t r, unsigned voff, unsigned soff) {
-    if constexpr (VEC == 2) __builtin_amdgcn_raw_buffer_store_b64(fdn_u32x2{__float_as_uint(f[0]), __float_as_uint(f[1])}, r, voff, soff, 0);
-    else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(f[0]), r, voff, soff, 0);
-}
+using f32x16 = fdn_f32x16;
 
 struct Args {
     const float *xi, *x1, *img, *w, *gamma, *beta, *w1m, *w3m, *w1a, *w3a;
@@ -251,14 +226,8 @@ int launch_fcaffn_in(Args a, hipStream_t s) {
     a.tiles_per_img = cdiv((long)a.H * a.W, 4 * 32 * VEC);
     a.total_tiles = a.B * a.tiles_per_img;
     auto kern = fcaffn_in_kernel<NCH, VEC>;
-    if (lds > 48 * 1024 && !fdn_allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return FDN_ERR_LAUNCH;
-    const int cus = fdn_device_cus();
-    if (cus <= 0) return FDN_ERR_LAUNCH;
-    int per_cu = 0;
-    if (!fdn_occupancy(&per_cu, reinterpret_cast<const void*>(kern), 256, lds) || per_cu < 1) per_cu = 1;
-    if (per_cu > 4) per_cu = 4;
-    int grid = cus * per_cu;
-    if (grid > a.total_tiles) grid = a.total_tiles;
+    const int grid = fdn_persistent_grid(kern, 256, lds, a.total_tiles, {true, 4, 0, 0});
+    if (grid < 0) return FDN_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);
     return fdn_launch_status();
 }

@@ -31,8 +31,8 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using f32x16 = fdn_f32x16;
+using f32x4 = fdn_f32x4;
 
 __device__ __forceinline__ void wave_sync_lds() {
     // LDS operations of one wave execute in order; this keeps the COMPILER from moving LDS accesses across the phase boundary

@@ -12,17 +12,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t mk_rsrc(const float* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ float bload(rsrc_t r, unsigned voff, unsigned soff) {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ void bstore(float v, rsrc_t r, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, soff, 0);
-}
+using f32x16 = fdn_f32x16;
 
 struct FoArgs {
     const float* o;        // [B][4E][P]: out1 | out2 | out3 | v_value
@@ -182,15 +172,7 @@ __global__ __launch_bounds__(NW * 64, SH <= 19 ? 2 : 1) void fdsa_out_kernel(FoA
 // groups are taken one after the other - v_value stays in registers, out_g is loaded (the next group while this one is
 // normalised and multiplied), its statistics come from registers (two-pass), and its slice of project_out accumulates
 // into the same two MFMA chains.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 bload2(rsrc_t r, unsigned voff, unsigned soff) {
-    const u32x2 u = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
-    return f32x2{__uint_as_float(u.x), __uint_as_float(u.y)};
-}
-__device__ __forceinline__ void bstore2(f32x2 v, rsrc_t r, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(v.x), __float_as_uint(v.y)}, r, voff, soff, 0);
-}
+using f32x2 = fdn_f32x2;
 
 // DB: prefetch the next group into a second register set (level 1); without it the other wave on the SIMD covers the
 // load latency (level 2: 76-channel groups, two 32-row tiles - a second set would not leave two waves per SIMD).
@@ -211,10 +193,6 @@ template <> struct PxT<2> { typedef f32x2 T; };
 template <> struct PxT<1> { typedef float T; };
 __device__ __forceinline__ float pcomp(float v, int) { return v; }
 __device__ __forceinline__ float pcomp(f32x2 v, int i) { return i ? v.y : v.x; }
-__device__ __forceinline__ float xsum32(float v) { return v + __shfl_xor(v, 32); }
-__device__ __forceinline__ f32x2 xsum32(f32x2 v) { return f32x2{v.x + __shfl_xor(v.x, 32), v.y + __shfl_xor(v.y, 32)}; }
-__device__ __forceinline__ float rsqrt_eps(float v) { return 1.0f / sqrtf(v + 1e-5f); }
-__device__ __forceinline__ f32x2 rsqrt_eps(f32x2 v) { return f32x2{1.0f / sqrtf(v.x + 1e-5f), 1.0f / sqrtf(v.y + 1e-5f)}; }
 __device__ __forceinline__ void mkpx(float& o, const f32x16 (&acc)[1], int r) { o = acc[0][r]; }
 __device__ __forceinline__ void mkpx(f32x2& o, const f32x16 (&acc)[2], int r) { o = f32x2{acc[0][r], acc[1][r]}; }
 __device__ __forceinline__ void bloadp(float& v, rsrc_t r, unsigned voff, unsigned soff) { v = bload(r, voff, soff); }
@@ -461,33 +439,24 @@ template <int SH, int MT, bool DB, bool IBF, int PX = 2, int NWV = NW, bool PBF 
 int launch_vec(FoArgs a, hipStream_t s) {
     const size_t lds = PBF ? (((6UL * 2 * SH + 3) & ~3UL) * sizeof(float) + 3UL * ((SH + 7) / 8) * MT * 3 * 64 * 16)
                            : (6UL * 2 * SH + 3UL * 2 * SH * (MT * 32 + 1)) * sizeof(float);
-    const int cus = fdn_device_cus();
-    if (cus <= 0) return FDN_ERR_LAUNCH;
-    if (lds > 48 * 1024 && !fdn_allow_dynamic_lds(reinterpret_cast<const void*>(fdsa_out_vec_kernel<SH, MT, DB, IBF, PX, NWV, PBF>), lds)) return FDN_ERR_LAUNCH;
     a.tiles_per_img = cdiv(a.P, NWV * 32 * PX);
     a.total_tiles = a.B * a.tiles_per_img;
-    int grid = cus * (NWV == 8 ? 1 : 2);
-    if (grid > a.total_tiles) grid = a.total_tiles;
+    auto kern = fdsa_out_vec_kernel<SH, MT, DB, IBF, PX, NWV, PBF>;
+    const int grid = fdn_persistent_grid(kern, NWV * 64, lds, a.total_tiles, {false, NWV == 8 ? 1 : 2, 0, 0});
+    if (grid < 0) return FDN_ERR_LAUNCH;
     if (PBF) fdn_note_bf16_launch();
-    hipLaunchKernelGGL((fdsa_out_vec_kernel<SH, MT, DB, IBF, PX, NWV, PBF>), dim3(grid), dim3(NWV * 64), lds, s, a);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NWV * 64), lds, s, a);
     return fdn_launch_status();
 }
 
 template <int SH, int MT>
 int launch(FoArgs a, hipStream_t s) {
     const size_t lds = (6UL * 2 * SH + 3UL * 2 * SH * (MT * 32 + 1)) * sizeof(float);
-    const int g_cus = fdn_device_cus();
-    if (g_cus <= 0) return FDN_ERR_LAUNCH;
     a.tiles_per_img = cdiv(a.P, NW * 32);
     a.total_tiles = a.B * a.tiles_per_img;
     auto kern = fdsa_out_kernel<SH, MT>;
-    if (lds > 48 * 1024 && !fdn_allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return FDN_ERR_LAUNCH;
-    int per_cu = (int)((160 * 1024) / lds);
-    const int want = SH <= 19 ? 2 : 1;
-    if (per_cu > want) per_cu = want;
-    if (per_cu < 1) per_cu = 1;
-    int grid = g_cus * per_cu;
-    if (grid > a.total_tiles) grid = a.total_tiles;
+    const int grid = fdn_persistent_grid(kern, NW * 64, lds, a.total_tiles, {false, SH <= 19 ? 2 : 1, 0, 160 * 1024});
+    if (grid < 0) return FDN_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, s, a);
     return fdn_launch_status();
 }

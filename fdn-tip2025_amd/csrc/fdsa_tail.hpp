@@ -13,22 +13,7 @@
 
 namespace {
 
-typedef __amdgpu_buffer_rsrc_t trsrc_t;
-__device__ __forceinline__ trsrc_t tl_rsrc(const float* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)bytes, 0x00020000);
-}
 constexpr int TL_SC1 = 16;                 // aux bit 4 = sc1 on gfx940+: served by L2, this CU's L1 bypassed
-__device__ __forceinline__ fdn_f32x2 tl_load2(trsrc_t r, unsigned voff, unsigned soff) {
-    const fdn_u32x2 u = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, TL_SC1);
-    return fdn_f32x2{__uint_as_float(u.x), __uint_as_float(u.y)};
-}
-__device__ __forceinline__ float tl_load1(trsrc_t r, unsigned voff, unsigned soff) {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, TL_SC1));
-}
-__device__ __forceinline__ fdn_f32x2 tl_xsum32(fdn_f32x2 v) { return fdn_f32x2{v.x + __shfl_xor(v.x, 32), v.y + __shfl_xor(v.y, 32)}; }
-__device__ __forceinline__ float tl_xsum32(float v) { return v + __shfl_xor(v, 32); }
-__device__ __forceinline__ fdn_f32x2 tl_rsqrt_eps(fdn_f32x2 v) { return fdn_f32x2{1.0f / sqrtf(v.x + 1e-5f), 1.0f / sqrtf(v.y + 1e-5f)}; }
-__device__ __forceinline__ float tl_rsqrt_eps(float v) { return 1.0f / sqrtf(v + 1e-5f); }
 
 // (dl * dl rounded, then added: fdsa_out_vec_kernel's select between the product and the sum keeps the two apart; without the select - FULL: every
 // channel of the group exists - the compiler would contract them into one fma and the statistics would round differently)
@@ -78,7 +63,7 @@ __device__ __forceinline__ void tl_ring_release(const TailIo& io) {
 template <int SH, bool PIN = false, int NT = 3, bool FULL = false>
 __device__ __forceinline__ void fdsa_tail_px2(const TailIo& io, const float* lds, const float* lds_pin = nullptr) {
     typedef fdn_f32x2 T;
-    typedef float f32x16 __attribute__((ext_vector_type(16)));
+    typedef fdn_f32x16 f32x16;
     constexpr int E2 = 2 * SH, WS = 33;
     const float* tg = lds;
     const float* tb = lds + 3 * E2;
@@ -90,21 +75,21 @@ __device__ __forceinline__ void fdsa_tail_px2(const TailIo& io, const float* lds
     const bool ok = io.tx0 + col < io.W;
     const unsigned pix = (unsigned)((io.ty0 + row) * io.W + io.tx0 + col);
     constexpr unsigned PI = 1024u;                                   // bytes per plane of the tile
-    const trsrc_t rg[3] = {tl_rsrc(io.scr, (unsigned)E * PI), tl_rsrc(io.scr + (long)E * 256, (unsigned)E * PI),
-                           tl_rsrc(io.scr + (long)2 * E * 256, (unsigned)E * PI)};
-    const trsrc_t rv = tl_rsrc(io.scr + (long)3 * E * 256, (unsigned)E * PI);
+    const rsrc_t rg[3] = {mk_rsrc(io.scr, (unsigned)E * PI), mk_rsrc(io.scr + (long)E * 256, (unsigned)E * PI),
+                          mk_rsrc(io.scr + (long)2 * E * 256, (unsigned)E * PI)};
+    const rsrc_t rv = mk_rsrc(io.scr + (long)3 * E * 256, (unsigned)E * PI);
     const unsigned voff = kh * PI + (unsigned)(row * 32 + col) * 4u;    // channel e = 2s + kh; e >= E reads 0 (outside the descriptor)
     const float invE = 1.0f / (float)E;
 
     T vv[SH], oa[SH], ob2[SH];
 #pragma unroll
     for (int s = 0; s < SH; ++s) {
-        vv[s] = tl_load2(rv, voff, (unsigned)(2 * s) * PI);
-        oa[s] = tl_load2(rg[0], voff, (unsigned)(2 * s) * PI);
+        vv[s] = bload2<TL_SC1>(rv, voff, (unsigned)(2 * s) * PI);
+        oa[s] = bload2<TL_SC1>(rg[0], voff, (unsigned)(2 * s) * PI);
     }
     const unsigned nb4 = (unsigned)N * P4;
-    const trsrc_t ro = tl_rsrc(io.y, nb4);
-    const trsrc_t rr = tl_rsrc(io.res ? io.res : io.y, io.res ? nb4 : 0u);
+    const rsrc_t ro = mk_rsrc(io.y, nb4);
+    const rsrc_t rr = mk_rsrc(io.res ? io.res : io.y, io.res ? nb4 : 0u);
     const unsigned vo = ok ? (4u * kh * P + pix) * 4u : 0x80000000u;
     T rres[16];
     f32x16 acc[2];
@@ -119,19 +104,19 @@ __device__ __forceinline__ void fdsa_tail_px2(const TailIo& io, const float* lds
         if (g < 2) {
             T* nxt = (g & 1) ? oa : ob2;
 #pragma unroll
-            for (int s = 0; s < SH; ++s) nxt[s] = tl_load2(rg[g + 1], voff, (unsigned)(2 * s) * PI);
+            for (int s = 0; s < SH; ++s) nxt[s] = bload2<TL_SC1>(rg[g + 1], voff, (unsigned)(2 * s) * PI);
         }
         T m = 0.f;
 #pragma unroll
         for (int s = 0; s < SH; ++s) m += cur[s];
-        m = tl_xsum32(m) * invE;
+        m = xsum32(m) * invE;
         T q = 0.f;
 #pragma unroll
         for (int s = 0; s < SH; ++s) {
             const T dl = cur[s] - m;
             q = tl_sq_acc<FULL>(q, dl, 2 * s + kh < E);
         }
-        const T rs = tl_rsqrt_eps(tl_xsum32(q) * invE);
+        const T rs = rsqrt_eps(xsum32(q) * invE);
 #pragma unroll
         for (int s = 0; s < SH; ++s) {
             asm volatile("" ::: "memory");
@@ -167,15 +152,15 @@ __device__ __forceinline__ void fdsa_tail_px2(const TailIo& io, const float* lds
     }
     if (io.stats_out || PIN) {
         T sq = 0.f;
-        const T mean = tl_xsum32(sm) / (float)N;
+        const T mean = xsum32(sm) / (float)N;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const T dl = outv[r] - mean;
             sq = tl_sq_acc<FULL>(sq, dl, (r & 3) + 8 * (r >> 2) + 4 * kh < N);
         }
-        const T rstd = tl_rsqrt_eps(tl_xsum32(sq) / (float)N);
+        const T rstd = rsqrt_eps(xsum32(sq) / (float)N);
         if (io.stats_out && kh == 0) {
-            const trsrc_t rs_ = tl_rsrc(io.stats_out, 2u * P4);
+            const rsrc_t rs_ = mk_rsrc(io.stats_out, 2u * P4);
             const unsigned vs = ok ? pix * 4u : 0x80000000u;
             __builtin_amdgcn_raw_buffer_store_b64(fdn_u32x2{__float_as_uint(mean.x), __float_as_uint(mean.y)}, rs_, vs, 0u, 0);
             __builtin_amdgcn_raw_buffer_store_b64(fdn_u32x2{__float_as_uint(rstd.x), __float_as_uint(rstd.y)}, rs_, vs, P4, 0);
@@ -209,7 +194,7 @@ __device__ __forceinline__ void fdsa_tail_px2(const TailIo& io, const float* lds
             }
             const fdn_u32x4* wpin = reinterpret_cast<const fdn_u32x4*>(lds_pin) + lane;
             const float* bpin = lds_pin + NT * 2 * 3 * 64 * 4;
-            const trsrc_t rh = tl_rsrc(io.h, (unsigned)io.Hd * P4);
+            const rsrc_t rh = mk_rsrc(io.h, (unsigned)io.Hd * P4);
             const unsigned vh = ok ? (4u * kh * P + pix) * 4u : 0x80000000u;
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
@@ -227,7 +212,7 @@ __device__ __forceinline__ void fdsa_tail_px2(const TailIo& io, const float* lds
                     ah[1] = fdn_mfma_split6(a3, Bf[1][ks], ah[1]);
                 }
                 if (io.h_bf16) {                                        // (uniform) bf16 storage: the pixel pair is one dword
-                    const trsrc_t rhb = tl_rsrc(io.h, (unsigned)io.Hd * P * 2u);
+                    const rsrc_t rhb = mk_rsrc(io.h, (unsigned)io.Hd * P * 2u);
                     const unsigned vhb = ok ? (4u * kh * P + pix) * 2u : 0x80000000u;
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
@@ -258,20 +243,20 @@ typedef __attribute__((address_space(3))) const fdn_u32x4* lds_cu4;
 // packed operands ([NT][4 k-steps][3 parts][64 lanes] x 16 bytes, then 32 NT bias floats) are read from the image in global memory (72 KB: L1 / L2 hits)
 template <int SH, int MT, bool FULL = false, bool PIN = false, int NT = 6>          // FULL: E == 2 SH and N == 32 MT (the stock level 2: E = 76, C = 64): no channel-range predicates
 __device__ FDN_TAIL_FN void fdsa_tail_px1(const TailIo& io, lds_cf tg, lds_cf tb, lds_cu4 W0, lds_cu4 W1, const float* gimg) {
-    typedef float f32x16 __attribute__((ext_vector_type(16)));
+    typedef fdn_f32x16 f32x16;
     constexpr int E2 = 2 * SH, NQ = (SH + 7) / 8;
     const int E = io.E, N = io.N;
     const unsigned P = io.P, P4 = P * 4u;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, kh = lane >> 5, ln = lane & 31;
     constexpr unsigned PI = 1024u;
-    const trsrc_t rg[3] = {tl_rsrc(io.scr, (unsigned)E * PI), tl_rsrc(io.scr + (long)E * 256, (unsigned)E * PI),
-                           tl_rsrc(io.scr + (long)2 * E * 256, (unsigned)E * PI)};
-    const trsrc_t rv = tl_rsrc(io.scr + (long)3 * E * 256, (unsigned)E * PI);
-    const trsrc_t rw2 = tl_rsrc(gimg + 512 + 2 * NQ * MT * 3 * 64 * 4, (unsigned)(NQ * MT * 3 * 64) * 16u);      // group 2's operands
+    const rsrc_t rg[3] = {mk_rsrc(io.scr, (unsigned)E * PI), mk_rsrc(io.scr + (long)E * 256, (unsigned)E * PI),
+                          mk_rsrc(io.scr + (long)2 * E * 256, (unsigned)E * PI)};
+    const rsrc_t rv = mk_rsrc(io.scr + (long)3 * E * 256, (unsigned)E * PI);
+    const rsrc_t rw2 = mk_rsrc(gimg + 512 + 2 * NQ * MT * 3 * 64 * 4, (unsigned)(NQ * MT * 3 * 64) * 16u);      // group 2's operands
     const float invE = 1.0f / (float)E;
     const unsigned nb4 = (unsigned)N * P4;
-    const trsrc_t ro = tl_rsrc(io.y, nb4);
-    const trsrc_t rr = tl_rsrc(io.res ? io.res : io.y, io.res ? nb4 : 0u);
+    const rsrc_t ro = mk_rsrc(io.y, nb4);
+    const rsrc_t rr = mk_rsrc(io.res ? io.res : io.y, io.res ? nb4 : 0u);
     const bool ok = io.tx0 + ln < io.W;
 
     float vv[SH], buf[2][SH];
@@ -282,8 +267,8 @@ __device__ FDN_TAIL_FN void fdsa_tail_px1(const TailIo& io, lds_cf tg, lds_cf tb
         asm volatile("" : "+s"(PIl));
 #pragma unroll
         for (int s = 0; s < SH; ++s) {
-            vv[s] = tl_load1(rv, voff, (unsigned)(2 * s) * PIl);
-            buf[0][s] = tl_load1(rg[0], voff, (unsigned)(2 * s) * PIl);
+            vv[s] = bload<TL_SC1>(rv, voff, (unsigned)(2 * s) * PIl);
+            buf[0][s] = bload<TL_SC1>(rg[0], voff, (unsigned)(2 * s) * PIl);
         }
     }
 #pragma unroll
@@ -311,19 +296,19 @@ __device__ FDN_TAIL_FN void fdsa_tail_px1(const TailIo& io, lds_cf tg, lds_cf tb
             asm volatile("" : "+s"(PIl));
             if (g < 2) {
 #pragma unroll
-                for (int s = 0; s < SH; ++s) nxt[s] = tl_load1(rg[g + 1], voff, (unsigned)(2 * s) * PIl);
+                for (int s = 0; s < SH; ++s) nxt[s] = bload<TL_SC1>(rg[g + 1], voff, (unsigned)(2 * s) * PIl);
             }
             float m = 0.f;
 #pragma unroll
             for (int s = 0; s < SH; ++s) m += cur[s];
-            m = tl_xsum32(m) * invE;
+            m = xsum32(m) * invE;
             float q = 0.f;
 #pragma unroll
             for (int s = 0; s < SH; ++s) {
                 const float dl = cur[s] - m;
                 q = tl_sq_acc<FULL>(q, dl, 2 * s + khl < E);
             }
-            const float rs = tl_rsqrt_eps(tl_xsum32(q) * invE);
+            const float rs = rsqrt_eps(xsum32(q) * invE);
 #pragma unroll
             for (int s = 0; s < SH; ++s) {
                 asm volatile("" ::: "memory");
@@ -334,8 +319,8 @@ __device__ FDN_TAIL_FN void fdsa_tail_px1(const TailIo& io, lds_cf tg, lds_cf tb
                 const unsigned voff1 = voff_of(1);
 #pragma unroll
                 for (int s = 0; s < SH; ++s) {
-                    vv[s] = tl_load1(rv, voff1, (unsigned)(2 * s) * PIl);
-                    nxt[s] = tl_load1(rg[0], voff1, (unsigned)(2 * s) * PIl);
+                    vv[s] = bload<TL_SC1>(rv, voff1, (unsigned)(2 * s) * PIl);
+                    nxt[s] = bload<TL_SC1>(rg[0], voff1, (unsigned)(2 * s) * PIl);
                 }
             }
             if (g == 2 && rnd == 1) tl_ring_release(io);      // the second row's last group is in registers
@@ -391,7 +376,7 @@ __device__ FDN_TAIL_FN void fdsa_tail_px1(const TailIo& io, lds_cf tg, lds_cf tb
             }
         if (io.stats_out || PIN) {
             float sq = 0.f;
-            const float mean = tl_xsum32(sm) / (float)N;
+            const float mean = xsum32(sm) / (float)N;
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -399,9 +384,9 @@ __device__ FDN_TAIL_FN void fdsa_tail_px1(const TailIo& io, lds_cf tg, lds_cf tb
                     const float dl = outv[mt][r] - mean;
                     sq = tl_sq_acc<FULL>(sq, dl, mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * khl < N);
                 }
-            const float rstd = tl_rsqrt_eps(tl_xsum32(sq) / (float)N);
+            const float rstd = rsqrt_eps(xsum32(sq) / (float)N);
             if (io.stats_out && kh == 0) {
-                const trsrc_t rs_ = tl_rsrc(io.stats_out, 2u * P4);
+                const rsrc_t rs_ = mk_rsrc(io.stats_out, 2u * P4);
                 const unsigned vs = ok ? pix * 4u : 0x80000000u;
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mean), rs_, vs, 0u, 0);
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(rstd), rs_, vs, P4, 0);
@@ -427,8 +412,8 @@ __device__ FDN_TAIL_FN void fdsa_tail_px1(const TailIo& io, lds_cf tg, lds_cf tb
                         Bf[ks][0][j] = p1, Bf[ks][1][j] = p2, Bf[ks][2][j] = p3;
                     }
                 }
-                const trsrc_t rpw = tl_rsrc(gimg + tl_image_floats_px1_c(SH, MT), (unsigned)(NT * 4 * 3 * 64 * 16 + NT * 32 * 4));
-                const trsrc_t rh = tl_rsrc(io.h, (unsigned)io.Hd * P4);
+                const rsrc_t rpw = mk_rsrc(gimg + tl_image_floats_px1_c(SH, MT), (unsigned)(NT * 4 * 3 * 64 * 16 + NT * 32 * 4));
+                const rsrc_t rh = mk_rsrc(io.h, (unsigned)io.Hd * P4);
                 const unsigned vh = ok ? (4u * kh * P + pix) * 4u : 0x80000000u;
                 auto aload = [&](int t, int ks, fdn_u32x4 (&a3)[3]) {
 #pragma unroll

@@ -12,17 +12,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t mk_rsrc(const float* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ float bload(rsrc_t r, unsigned voff, unsigned soff) {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ void bstore(float v, rsrc_t r, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, soff, 0);
-}
+using f32x16 = fdn_f32x16;
 constexpr int TR = 8, TC = 32;            // pixel tile: one row per wave
 constexpr int HR = TR + 2, HC = TC + 2;   // halo tile
 constexpr int HPL = HR * HC;              // 340 floats per plane
@@ -225,7 +215,6 @@ __global__ __launch_bounds__(NT) void ffn_tail_kernel(FtArgs a) {
 // ------------------------------------------------------------------------------------------------
 constexpr int SW_TC = 64;                 // tile columns (two 32-column wave strips)
 constexpr int SW_LS = 72;                 // LDS row stride of a halo plane, in (A, B) cells: left halo at 3, interior from 4 (16-byte lanes), right halo at 68
-constexpr unsigned SW_OOB = 0x80000000u;
 
 // (round 4) The two source planes of a pair live in LDS as ONE plane of (A, B) cells and the taps as (wA, wB) pairs: a window cell is
 // one 8-byte read and both stencils advance in one v_pk_fma_f32 - 36 packed FMAs per pair and lane where there were 72 scalar ones.
@@ -244,7 +233,7 @@ __device__ __forceinline__ void ffn_tail_epilogue(const FtArgs& a, f32x16 (&acc)
         const int gy = ty0 + r0 + i;
         const bool ok = gy < H && gx < W;
         const unsigned pix = ok ? (unsigned)(gy * W + gx) : 0u;
-        const unsigned vo = ok ? (4u * kh * P + pix) * 4u : SW_OOB;
+        const unsigned vo = ok ? (4u * kh * P + pix) * 4u : OOB;
         float rres[MT][16];
 #pragma unroll
         for (int t = 0; t < MT; ++t)
@@ -315,14 +304,14 @@ __global__ __launch_bounds__(256, (R * MT <= 8 && !(IBF && CODD && MT == 2)) ? 2
         const int r = idx >> 4, c4 = idx & 15;
         const int y = ty0 - 1 + r, xx = tx0 + 4 * c4;
         const bool ok = idx < NV4 && y >= 0 && y < H && xx < W;
-        g4[i] = ok ? (unsigned)(y * W + xx) * IES : SW_OOB;
+        g4[i] = ok ? (unsigned)(y * W + xx) * IES : OOB;
         s4[i] = idx < NV4 ? r * SW_LS + 4 + 4 * c4 : HRW * SW_LS;
     }
     {
         const int er = tid >> 1, ec = (tid & 1) ? SW_TC + 1 : 0;      // image column tx0 - 1 + ec lives in cell 3 + ec
         const int ey = ty0 - 1 + er, ex = tx0 - 1 + ec;
         const bool eok = tid < 2 * HRW && ey >= 0 && ey < H && ex >= 0 && ex < W;
-        ge = eok ? (unsigned)(ey * W + ex) * IES : SW_OOB;
+        ge = eok ? (unsigned)(ey * W + ex) * IES : OOB;
         se = tid < 2 * HRW ? er * SW_LS + 3 + ec : HRW * SW_LS;
     }
     // two register stages: the planes of pair m + 2 are requested while pair m is evaluated (one pair of arithmetic is ~0.4 us,
@@ -346,10 +335,10 @@ __global__ __launch_bounds__(256, (R * MT <= 8 && !(IBF && CODD && MT == 2)) ? 2
     {
         const int par = tid / 20, i = tid - par * 20, tap = i >> 1;
         dw_par = par;
-        vdw = (tid < 40 && tap < 9) ? (unsigned)((((i & 1) ? C : 0) + par) * 9 + tap) * 4u : SW_OOB;      // + 72 m: taps of channel 2 m + par, (wA, wB) interleaved
+        vdw = (tid < 40 && tap < 9) ? (unsigned)((((i & 1) ? C : 0) + par) * 9 + tap) * 4u : OOB;      // + 72 m: taps of channel 2 m + par, (wA, wB) interleaved
         const int u = tid - 64, n = u % (MT * 32);
         pw_par = u / (MT * 32);
-        vpw = (u >= 0 && u < 2 * MT * 32 && n < N) ? (unsigned)(n * C + pw_par) * 4u : SW_OOB;            // + 8 m: w[n][2 m + par] (threads 64 ..)
+        vpw = (u >= 0 && u < 2 * MT * 32 && n < N) ? (unsigned)(n * C + pw_par) * 4u : OOB;            // + 8 m: w[n][2 m + par] (threads 64 ..)
     }
     auto fetch = [&](int m, Stage& st) {
         float (&q4)[3][V4T][4] = st.q4;
@@ -369,8 +358,8 @@ __global__ __launch_bounds__(256, (R * MT <= 8 && !(IBF && CODD && MT == 2)) ? 2
         qe[1] = st_load1<IBF>(ri, ge, (unsigned)pb0 * hwi);
         if (codd) qe[2] = st_load1<IBF>(ri, ge, (unsigned)pb1 * hwi);
         // depthwise taps of channels 2m, 2m + 1 ([parity][tap](wA, wB), threads 0-39) / the projection's columns 2m, 2m + 1 (waves 1 .. MT)
-        pdw = bload(rd, (!codd || 2 * m + dw_par < C) ? vdw : SW_OOB, (unsigned)(72 * m));
-        st.pw = bload(rw_, (!codd || 2 * m + pw_par < C) ? vpw : SW_OOB, (unsigned)(8 * m));
+        pdw = bload(rd, (!codd || 2 * m + dw_par < C) ? vdw : OOB, (unsigned)(72 * m));
+        st.pw = bload(rw_, (!codd || 2 * m + pw_par < C) ? vpw : OOB, (unsigned)(8 * m));
     };
     auto stash = [&](int buf, const Stage& st) {
         const float (&q4)[3][V4T][4] = st.q4;
@@ -480,13 +469,11 @@ int launch_sw(FtArgs a, hipStream_t s) {
 
 template <int MT>
 int launch(FtArgs a, hipStream_t s) {
-    const int g_cus = fdn_device_cus();
-    if (g_cus <= 0) return FDN_ERR_LAUNCH;
     a.tiles_x = cdiv(a.W, TC);
     a.tiles_per_img = a.tiles_x * cdiv(a.H, TR);
     a.total_tiles = a.B * a.tiles_per_img;
-    int grid = g_cus * 2;
-    if (grid > a.total_tiles) grid = a.total_tiles;
+    const int grid = fdn_persistent_grid(ffn_tail_kernel<MT>, NT, 0, a.total_tiles, {false, 2, 0, 0});
+    if (grid < 0) return FDN_ERR_LAUNCH;
     hipLaunchKernelGGL(ffn_tail_kernel<MT>, dim3(grid), dim3(NT), 0, s, a);
     return fdn_launch_status();
 }

@@ -857,15 +857,8 @@ __global__ __launch_bounds__(NT, (INPL ? 2 : 1)) void fft_cols_kernel(ColArgs a,
 using fftr::f2;
 using fftr::sfor;
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t cols_rsrc(const void* base, long bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)(bytes > 0x7FFFFFFFL ? 0x7FFFFFFFL : bytes), 0x00020000);
-}
-__device__ __forceinline__ f2 bload_f2(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    const fdn_u32x2 u = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
-    return f2{__uint_as_float(u.x), __uint_as_float(u.y)};
-}
-__device__ __forceinline__ void bstore_f2(f2 v, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_buffer_store_b64(fdn_u32x2{__float_as_uint(v.x), __float_as_uint(v.y)}, r, voff, soff, 0);
+__device__ __forceinline__ rsrc_t cols_rsrc(const void* base, long bytes) {      // (a column set may pass 2 GiB: clamped to the field)
+    return mk_rsrc(base, (unsigned)(bytes > 0x7FFFFFFFL ? 0x7FFFFFFFL : bytes));
 }
 
 template <typename K>
@@ -921,7 +914,7 @@ __global__ __launch_bounds__((ColPlan<R, P>::NT), (3 * ColPlan<R, P>::lds <= 160
 
     if (MODE != COL_INV_POLAR && io) {
         f2 u[R];
-        sfor<0, R>([&](auto n1) { u[decltype(n1)::value] = bload_f2(rz, zoff, (unsigned)decltype(n1)::value * zstep); });
+        sfor<0, R>([&](auto n1) { u[decltype(n1)::value] = bload2(rz, zoff, (unsigned)decltype(n1)::value * zstep); });
         fftr::dft_nat<R, false>(u);
         sfor<0, R>([&](auto k1) { Y[decltype(k1)::value * KS + tid] = u[decltype(k1)::value]; });
     }
@@ -1093,7 +1086,7 @@ __global__ __launch_bounds__((ColPlan<R, P>::NT), (3 * ColPlan<R, P>::lds <= 160
         f2 u[R];
         sfor<0, R>([&](auto k) { u[decltype(k)::value] = Y[decltype(k)::value * KS + tid]; });
         fftr::dft_nat<R, true>(u);
-        if (live) sfor<0, R>([&](auto n1) { bstore_f2(u[decltype(n1)::value], rz, zoff, (unsigned)decltype(n1)::value * zstep); });
+        if (live) sfor<0, R>([&](auto n1) { bstore2(u[decltype(n1)::value], rz, zoff, (unsigned)decltype(n1)::value * zstep); });
     }
 }
 
@@ -1367,7 +1360,7 @@ __global__ __launch_bounds__(256, 2) void rfft_rows_rp_kernel(const float* __res
         const __amdgpu_buffer_rsrc_t rin = cols_rsrc(in + row0 * W, (long)nrow * W * 4);
         const unsigned voff = (unsigned)(rwc * W + 2 * n2) * 4u;
         f2 u[R1];
-        sfor<0, R1>([&](auto n1) { u[decltype(n1)::value] = bload_f2(rin, voff, (unsigned)(decltype(n1)::value * P * 8)); });
+        sfor<0, R1>([&](auto n1) { u[decltype(n1)::value] = bload2(rin, voff, (unsigned)(decltype(n1)::value * P * 8)); });
         if constexpr (LN) {
             const long row = row0 + rwc, plane = row / lnp.H;
             const int h = (int)(row - plane * lnp.H), c = (int)(plane % lnp.C);
@@ -1381,8 +1374,8 @@ __global__ __launch_bounds__(256, 2) void rfft_rows_rp_kernel(const float* __res
             f2 mu[R1], rs[R1];
             sfor<0, R1>([&](auto n1) {
                 constexpr int N1 = decltype(n1)::value;
-                mu[N1] = bload_f2(rs_, so, (unsigned)(N1 * P * 8));
-                rs[N1] = bload_f2(rs_, so + (unsigned)HW * 4u, (unsigned)(N1 * P * 8));
+                mu[N1] = bload2(rs_, so, (unsigned)(N1 * P * 8));
+                rs[N1] = bload2(rs_, so + (unsigned)HW * 4u, (unsigned)(N1 * P * 8));
             });
             sfor<0, R1>([&](auto n1) {
                 constexpr int N1 = decltype(n1)::value;
@@ -1539,12 +1532,12 @@ __global__ __launch_bounds__(256, 2) void irfft_rows_rp_kernel(const float2* __r
             const __amdgpu_buffer_rsrc_t rr = cols_rsrc(res ? res + row0 * W : out, res ? (long)nrow * W * 4 : 0);
             const unsigned voff = (unsigned)(rw * W + 2 * n2) * 4u;
             f2 r[R1];
-            if (res) sfor<0, R1>([&](auto n1) { r[decltype(n1)::value] = bload_f2(rr, voff, (unsigned)(decltype(n1)::value * P * 8)); });
+            if (res) sfor<0, R1>([&](auto n1) { r[decltype(n1)::value] = bload2(rr, voff, (unsigned)(decltype(n1)::value * P * 8)); });
             sfor<0, R1>([&](auto n1) {
                 constexpr int N1 = decltype(n1)::value;
                 f2 x = u[N1] * scale;
                 if (res) x += alpha * r[N1];
-                bstore_f2(x, ro, voff, (unsigned)(N1 * P * 8));
+                bstore2(x, ro, voff, (unsigned)(N1 * P * 8));
             });
         }
     }

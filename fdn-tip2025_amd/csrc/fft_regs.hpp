@@ -16,7 +16,7 @@
 
 namespace fftr {
 
-typedef float f2 __attribute__((ext_vector_type(2)));
+typedef fdn_f32x2 f2;
 __device__ __forceinline__ f2 mul_pi(f2 a) { return f2{-a.y, a.x}; }      // * (+i)
 __device__ __forceinline__ f2 mul_ni(f2 a) { return f2{a.y, -a.x}; }      // * (-i)
 __device__ __forceinline__ f2 cmul(f2 a, f2 b) { return f2{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }

@@ -28,7 +28,7 @@
 namespace {
 
 constexpr int KC = 32;     // K chunk (16 MFMA k-steps)
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using f32x16 = fdn_f32x16;
 
 // The activation / epilogue kind are wave-uniform runtime values of the descriptor.  Tested per element they cost a chain
 // of scalar compare-and-branch per output value (the switch of apply_act alone is ~8 branches: 5.3k of a 23.5k-cycle output
@@ -57,18 +57,6 @@ struct Geo {
     int resident;          // whole K x (MT*32) weight slice kept in LDS
     int bias_off;          // float offset of the bias table in dynamic LDS (generic kernel)
 };
-
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ rsrc_t mk_rsrc(const float* base, unsigned bytes) {
-    // raw buffer, stride 0: offsets >= bytes read 0 / drop the store (K, N and plane tails for free)
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ float bload(rsrc_t r, unsigned voff, unsigned soff) {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ void bstore(float v, rsrc_t r, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, soff, 0);
-}
 
 template <int MT, int PRO, int NW, bool EARLY>
 __global__ __launch_bounds__(NW * 64, (NW == 4 && !EARLY) ? ((MT <= 2 && PRO == FDN_PRO_NONE) ? 3 : 2) : 1) void conv1x1_kernel(fdn_conv1x1_desc d, Geo g) {
@@ -530,29 +518,7 @@ __global__ __launch_bounds__(NW * 64) void conv1x1_smallk_kernel(fdn_conv1x1_des
 // 256 contiguous bytes of a channel plane instead of 128 - the dword form stops at ~3.8 TB/s, 16-byte lanes reach ~5
 // (same effect as in norm.hip).  Register v of a loaded vector is the B operand of MFMA chain v; the VEC chains share
 // every A operand read from LDS.  Plain / LN prologue, no epilogue operand, one input segment, P % VEC == 0.
-template <int VEC> struct VecT;
-template <> struct VecT<2> { typedef float type __attribute__((ext_vector_type(2))); };
-template <> struct VecT<4> { typedef float type __attribute__((ext_vector_type(4))); };
-template <int VEC>
-__device__ __forceinline__ typename VecT<VEC>::type bloadv(rsrc_t r, unsigned voff, unsigned soff) {
-    typedef unsigned uv __attribute__((ext_vector_type(VEC)));
-    uv u;
-    if constexpr (VEC == 4) u = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
-    else u = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
-    typename VecT<VEC>::type f;
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) f[i] = __uint_as_float(u[i]);
-    return f;
-}
-template <int VEC>
-__device__ __forceinline__ void bstorev(typename VecT<VEC>::type f, rsrc_t r, unsigned voff, unsigned soff) {
-    typedef unsigned uv __attribute__((ext_vector_type(VEC)));
-    uv u;
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) u[i] = __float_as_uint(f[i]);
-    if constexpr (VEC == 4) __builtin_amdgcn_raw_buffer_store_b128(u, r, voff, soff, 0);
-    else __builtin_amdgcn_raw_buffer_store_b64(u, r, voff, soff, 0);
-}
+// (bloadv / bstorev: buffer_io.hpp)
 
 // the same for an activation tensor kept in bf16 STORAGE (BF = true: VEC bf16 values = VEC * 2 bytes per lane, widened to fp32 /
 // rounded to nearest-even; the arithmetic is fp32 either way)
@@ -1213,10 +1179,7 @@ int pick_mt(int N) {
     return best;
 }
 
-// launch-time facts are cached per (kernel, device) in capi.hip: no occupancy / attribute query on the hot path
-#define FDN_NUM_CU_OR_FAIL()               \
-    const int g_num_cu = fdn_device_cus(); \
-    if (g_num_cu <= 0) return FDN_ERR_LAUNCH;
+// launch-time facts are cached per (kernel, device) in capi.hip (fdn_persistent_grid): no occupancy / attribute query on the hot path
 
 template <int MT, int PRO, int NW, bool EARLY>
 int launch(const fdn_conv1x1_desc& d, hipStream_t s) {
@@ -1231,15 +1194,10 @@ int launch(const fdn_conv1x1_desc& d, hipStream_t s) {
     g.tiles_per_img = cdiv(d.P, NW * 32);
     g.total_tiles = d.B * g.tiles_per_img;
     auto kern = conv1x1_kernel<MT, PRO, NW, EARLY>;
-    if (lds > 48 * 1024 && !fdn_allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return FDN_ERR_LAUNCH;
-    FDN_NUM_CU_OR_FAIL()
-    // persistent grid: as many workgroups as can be co-resident (LDS / register limited), capped by the work
-    int per_cu = 0;
-    if (!fdn_occupancy(&per_cu, reinterpret_cast<const void*>(kern), NW * 64, lds)) per_cu = 1;
-    if (per_cu * NW > 16) per_cu = 16 / NW;                     // 4 waves per SIMD are enough to hide the loads
-    if (per_cu < 1) per_cu = 1;
-    int grid = g_num_cu * per_cu;
-    if (grid > g.total_tiles) grid = g.total_tiles;
+    // persistent grid: as many workgroups as can be co-resident (LDS / register limited), capped by the work;
+    // 16 waves per CU (4 per SIMD) are enough to hide the loads
+    const int grid = fdn_persistent_grid(kern, NW * 64, lds, g.total_tiles, {true, 0, 16, 0});
+    if (grid < 0) return FDN_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, s, d, g);
     return fdn_launch_status();
 }
@@ -1248,19 +1206,14 @@ template <int NCH, int PRO>
 int launch_smallk(const fdn_conv1x1_desc& d, hipStream_t s) {
     const int ntiles = (d.N + 31) / 32;
     const size_t lds = (2UL * NCH * KC + (size_t)NCH * KC * (ntiles * 32 + 1) + ntiles * 32) * sizeof(float);
-    FDN_NUM_CU_OR_FAIL()
     constexpr int NW = 8;
     Geo g;
     g.resident = 1;
     g.tiles_per_img = cdiv(d.P, NW * 32);
     g.total_tiles = d.B * g.tiles_per_img;
     auto kern = conv1x1_smallk_kernel<NCH, PRO, NW>;
-    if (lds > 48 * 1024 && !fdn_allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return FDN_ERR_LAUNCH;
-    int per_cu = (int)((160 * 1024) / lds);
-    if (per_cu > 3) per_cu = 3;
-    if (per_cu < 1) per_cu = 1;
-    int grid = g_num_cu * per_cu;
-    if (grid > g.total_tiles) grid = g.total_tiles;
+    const int grid = fdn_persistent_grid(kern, NW * 64, lds, g.total_tiles, {false, 3, 0, 160 * 1024});
+    if (grid < 0) return FDN_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, s, d, g);
     return fdn_launch_status();
 }
@@ -1269,14 +1222,14 @@ template <int NCH, int PRO>
 int launch_smallk_stream(const fdn_conv1x1_desc& d, hipStream_t s) {
     constexpr int NW = 8;
     const size_t lds = (2UL * NCH * KC + 2UL * NCH * KC * 33 + ((d.N + 31) / 32) * 32) * sizeof(float);
-    FDN_NUM_CU_OR_FAIL()
     Geo g;
     g.resident = 0;
     g.tiles_per_img = cdiv(d.P, NW * 32);
     g.total_tiles = d.B * g.tiles_per_img;
-    int grid = g_num_cu;                                           // 8 waves x ~190 VGPRs: one workgroup per CU
-    if (grid > g.total_tiles) grid = g.total_tiles;
-    hipLaunchKernelGGL((conv1x1_smallk_stream_kernel<NCH, PRO, NW>), dim3(grid), dim3(NW * 64), lds, s, d, g);
+    auto kern = conv1x1_smallk_stream_kernel<NCH, PRO, NW>;
+    const int grid = fdn_persistent_grid(kern, NW * 64, lds, g.total_tiles, {false, 1, 0, 0});   // 8 waves x ~190 VGPRs: one workgroup per CU
+    if (grid < 0) return FDN_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, s, d, g);
     return fdn_launch_status();
 }
 
@@ -1284,44 +1237,49 @@ template <int NCH, int PRO, int VEC, bool TAIL = false, bool XBF = false, bool O
 int launch_smallk_vec(const fdn_conv1x1_desc& d, hipStream_t s) {
     const int ntiles = (d.N + 31) / 32;
     const size_t lds = (2UL * NCH * KC + (size_t)NCH * KC * (ntiles * 32 + 1) + ntiles * 32) * sizeof(float);
-    FDN_NUM_CU_OR_FAIL()
     Geo g;
     g.resident = 1;
     g.tiles_per_img = cdiv(d.P, 4 * 32 * VEC);
     g.total_tiles = d.B * g.tiles_per_img;
     auto kern = conv1x1_smallk_vec_kernel<NCH, PRO, VEC, TAIL, XBF, OBF>;
-    if (lds > 48 * 1024 && !fdn_allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return FDN_ERR_LAUNCH;
-    int per_cu = 0;
-    if (!fdn_occupancy(&per_cu, reinterpret_cast<const void*>(kern), 256, lds) || per_cu < 1)
-        per_cu = 1;
-    if (per_cu > 4) per_cu = 4;
-    int grid = g_num_cu * per_cu;
-    if (grid > g.total_tiles) grid = g.total_tiles;
+    const int grid = fdn_persistent_grid(kern, 256, lds, g.total_tiles, {true, 4, 0, 0});
+    if (grid < 0) return FDN_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, d, g);
     return fdn_launch_status();
+}
+
+// 8- / 16-byte lanes: P and the batch strides in whole 16-byte units, x, out and the operands the form reads or writes besides
+// (p2, p3: null = none) 16-byte aligned
+bool vec_aligned(const fdn_conv1x1_desc& d, const void* p2 = nullptr, const void* p3 = nullptr) {
+    if (d.P % 4 != 0 || d.xbs[0] % 4 != 0 || d.obs % 4 != 0) return false;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d.x[0]) | reinterpret_cast<uintptr_t>(d.out) | reinterpret_cast<uintptr_t>(p2) | reinterpret_cast<uintptr_t>(p3);
+    return (a & 15) == 0;
+}
+// the vectorised project_out forms: residual or no epilogue operand, statistics allowed
+bool vec_out_ok(const fdn_conv1x1_desc& d) {
+    if (d.epi != FDN_EPI_NONE && d.epi != FDN_EPI_RES) return false;
+    if (d.epi == FDN_EPI_RES && d.rbs % 4 != 0) return false;
+    return vec_aligned(d, d.epi == FDN_EPI_RES ? d.res : nullptr, d.stats_out);
 }
 
 // the vectorised kernel covers: small-K shapes (see smallk_ok) with one segment, no epilogue operand, plain / LN prologue,
 // P a multiple of 4 and 16-byte aligned tensors
 bool smallk_vec_ok(const fdn_conv1x1_desc& d) {
     if (d.kseg[1] > 0 || d.kseg[2] > 0 || d.epi != FDN_EPI_NONE || (d.pro != FDN_PRO_NONE && d.pro != FDN_PRO_LN)) return false;
-    if (d.P % 4 != 0 || d.xbs[0] % 4 != 0 || d.obs % 4 != 0) return false;
-    uintptr_t a = reinterpret_cast<uintptr_t>(d.x[0]) | reinterpret_cast<uintptr_t>(d.out);
-    if (d.pro != FDN_PRO_NONE) a |= reinterpret_cast<uintptr_t>(d.stats);
-    return (a & 15) == 0;
+    return vec_aligned(d, d.pro != FDN_PRO_NONE ? d.stats : nullptr);
 }
 
 template <int NCH, int PRO>
 int launch_smallk_stream_vec(const fdn_conv1x1_desc& d, hipStream_t s) {
     const size_t lds = (2UL * NCH * KC + 2UL * NCH * KC * 33 + ((d.N + 31) / 32) * 32) * sizeof(float);
-    FDN_NUM_CU_OR_FAIL()
     Geo g;
     g.resident = 0;
     g.tiles_per_img = cdiv(d.P, 8 * 32 * 2);
     g.total_tiles = d.B * g.tiles_per_img;
-    int grid = g_num_cu;
-    if (grid > g.total_tiles) grid = g.total_tiles;
-    hipLaunchKernelGGL((conv1x1_smallk_stream_vec_kernel<NCH, PRO>), dim3(grid), dim3(512), lds, s, d, g);
+    auto kern = conv1x1_smallk_stream_vec_kernel<NCH, PRO>;
+    const int grid = fdn_persistent_grid(kern, 512, lds, g.total_tiles, {false, 1, 0, 0});
+    if (grid < 0) return FDN_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, d, g);
     return fdn_launch_status();
 }
 
@@ -1337,14 +1295,8 @@ int launch_kstream_vec(const fdn_conv1x1_desc& d, hipStream_t s) {
     g.tiles_per_img = cdiv(d.P, 4 * 32 * 2);
     g.total_tiles = d.B * g.tiles_per_img;
     auto kern = conv1x1_kstream_vec_kernel<MT, XBF>;
-    if (lds > 48 * 1024 && !fdn_allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return FDN_ERR_LAUNCH;
-    FDN_NUM_CU_OR_FAIL()
-    int per_cu = 0;
-    if (!fdn_occupancy(&per_cu, reinterpret_cast<const void*>(kern), 256, lds) || per_cu < 1)
-        per_cu = 1;
-    if (per_cu > 4) per_cu = 4;
-    int grid = g_num_cu * per_cu;
-    if (grid > g.total_tiles) grid = g.total_tiles;
+    const int grid = fdn_persistent_grid(kern, 256, lds, g.total_tiles, {true, 4, 0, 0});
+    if (grid < 0) return FDN_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, d, g);
     return fdn_launch_status();
 }
@@ -1352,12 +1304,7 @@ int launch_kstream_vec(const fdn_conv1x1_desc& d, hipStream_t s) {
 // plain deep-K convs for the 8-byte-lane K-streaming kernel
 bool kstream_vec_ok(const fdn_conv1x1_desc& d) {
     if (d.pro != FDN_PRO_NONE || d.kseg[1] > 0 || d.kseg[2] > 0 || d.K <= 96 || d.N > 96) return false;   // (N = 128 spills: slower)
-    if (d.epi != FDN_EPI_NONE && d.epi != FDN_EPI_RES) return false;
-    if (d.P % 4 != 0 || d.xbs[0] % 4 != 0 || d.obs % 4 != 0 || (d.epi == FDN_EPI_RES && d.rbs % 4 != 0)) return false;
-    uintptr_t a = reinterpret_cast<uintptr_t>(d.x[0]) | reinterpret_cast<uintptr_t>(d.out);
-    if (d.epi == FDN_EPI_RES) a |= reinterpret_cast<uintptr_t>(d.res);
-    if (d.stats_out) a |= reinterpret_cast<uintptr_t>(d.stats_out);
-    return (a & 15) == 0;                          // measured: 172 -> 64 at level 2 10.2 -> 7.0 ms (71 TFLOP/s)
+    return vec_out_ok(d);                          // measured: 172 -> 64 at level 2 10.2 -> 7.0 ms (71 TFLOP/s)
 }
 
 // K <= 128, N >= 2K, single input segment, plain/LN prologue, no muladd epilogue, weights too big for LDS
@@ -1372,12 +1319,7 @@ bool smallk_stream_ok(const fdn_conv1x1_desc& d) {
 // epilogue operand, statistics allowed
 bool narrow_vec_ok(const fdn_conv1x1_desc& d) {
     if (d.K > 96 || d.N > 32 || d.pro != FDN_PRO_NONE || d.kseg[1] > 0 || d.kseg[2] > 0) return false;
-    if (d.epi != FDN_EPI_NONE && d.epi != FDN_EPI_RES) return false;
-    if (d.P % 4 != 0 || d.xbs[0] % 4 != 0 || d.obs % 4 != 0 || (d.epi == FDN_EPI_RES && d.rbs % 4 != 0)) return false;
-    uintptr_t a = reinterpret_cast<uintptr_t>(d.x[0]) | reinterpret_cast<uintptr_t>(d.out);
-    if (d.epi == FDN_EPI_RES) a |= reinterpret_cast<uintptr_t>(d.res);
-    if (d.stats_out) a |= reinterpret_cast<uintptr_t>(d.stats_out);
-    return (a & 15) == 0;
+    return vec_out_ok(d);
 }
 
 // true when the small-K kernel covers this problem
@@ -1387,6 +1329,37 @@ bool smallk_ok(const fdn_conv1x1_desc& d) {
     const int nch = (d.K + KC - 1) / KC, ntiles = (d.N + 31) / 32;
     const size_t lds = (2UL * nch * KC + (size_t)nch * KC * (ntiles * 32 + 1)) * sizeof(float);
     return lds <= 100 * 1024;
+}
+
+// The three pixel-pair ladders of fdn_conv1x1, for fp32 and for bf16 storage of the one operand the form allows (XBF: input, OBF: output).
+template <bool XBF>
+int launch_kstream_by_tiles(const fdn_conv1x1_desc& d, hipStream_t s) {
+    const int tiles = (d.N + 31) / 32;
+    if (tiles == 1) return launch_kstream_vec<1, XBF>(d, s);
+    if (tiles == 2) return launch_kstream_vec<2, XBF>(d, s);
+    return launch_kstream_vec<3, XBF>(d, s);
+}
+template <bool XBF>
+int launch_narrow_by_chunks(const fdn_conv1x1_desc& d, hipStream_t s) {
+    if (d.K <= KC) return launch_smallk_vec<1, FDN_PRO_NONE, 2, true, XBF, false>(d, s);
+    if (d.K <= 2 * KC) return launch_smallk_vec<2, FDN_PRO_NONE, 2, true, XBF, false>(d, s);
+    return launch_smallk_vec<3, FDN_PRO_NONE, 2, true, XBF, false>(d, s);
+}
+// measured (tools/bench_kernels.py to_hidden ffn_in, B=8 720p): 8-byte lanes win for K <= 32 (32->152: 1.65 -> 1.44 ms,
+// 32->86: 0.92 -> 0.76 ms) and for K <= 64 while the weight matrix leaves room for 3 workgroups per CU (64->172:
+// 0.74 -> 0.59 ms; 64->304 is slower vectorised: FDN_ERR_UNSUPPORTED = not taken); 16-byte lanes spill with the LN prologue
+template <bool OBF>
+int launch_smallk_vec_by_chunks(const fdn_conv1x1_desc& d, hipStream_t s) {
+    const int ntiles = (d.N + 31) / 32;
+    if (d.K <= KC) {
+        if (d.pro == FDN_PRO_LN) return launch_smallk_vec<1, FDN_PRO_LN, 2, false, false, OBF>(d, s);       // (16-byte lanes measure the same here)
+        return launch_smallk_vec<1, FDN_PRO_NONE, 2, false, false, OBF>(d, s);       // (8-byte lanes only: the kernel static_asserts VEC == 2)
+    }
+    if ((2UL * 2 * KC + 2UL * KC * (ntiles * 32 + 1)) * sizeof(float) <= 52 * 1024) {
+        if (d.pro == FDN_PRO_LN) return launch_smallk_vec<2, FDN_PRO_LN, 2, false, false, OBF>(d, s);
+        return launch_smallk_vec<2, FDN_PRO_NONE, 2, false, false, OBF>(d, s);
+    }
+    return FDN_ERR_UNSUPPORTED;
 }
 
 template <int PRO>
@@ -1464,30 +1437,11 @@ extern "C" int fdn_conv1x1(const fdn_conv1x1_desc* dp, fdn_stream_t stream) {
     if (d.x_bf16 || d.out_bf16) {
         if ((d.x_bf16 && d.out_bf16) || own_stats) return FDN_ERR_UNSUPPORTED;
         if (d.x_bf16) {
-            if (kstream_vec_ok(d)) {
-                const int tiles = (d.N + 31) / 32;
-                if (tiles == 1) return launch_kstream_vec<1, true>(d, s);
-                if (tiles == 2) return launch_kstream_vec<2, true>(d, s);
-                return launch_kstream_vec<3, true>(d, s);
-            }
-            if (narrow_vec_ok(d)) {
-                if (d.K <= KC) return launch_smallk_vec<1, FDN_PRO_NONE, 2, true, true, false>(d, s);
-                if (d.K <= 2 * KC) return launch_smallk_vec<2, FDN_PRO_NONE, 2, true, true, false>(d, s);
-                return launch_smallk_vec<3, FDN_PRO_NONE, 2, true, true, false>(d, s);
-            }
+            if (kstream_vec_ok(d)) return launch_kstream_by_tiles<true>(d, s);
+            if (narrow_vec_ok(d)) return launch_narrow_by_chunks<true>(d, s);
             return FDN_ERR_UNSUPPORTED;
         }
-        if (smallk_ok(d) && smallk_vec_ok(d)) {
-            const int ntiles = (d.N + 31) / 32;
-            if (d.K <= KC) {
-                if (d.pro == FDN_PRO_LN) return launch_smallk_vec<1, FDN_PRO_LN, 2, false, false, true>(d, s);
-                return launch_smallk_vec<1, FDN_PRO_NONE, 2, false, false, true>(d, s);
-            }
-            if ((2UL * 2 * KC + 2UL * KC * (ntiles * 32 + 1)) * sizeof(float) <= 52 * 1024) {
-                if (d.pro == FDN_PRO_LN) return launch_smallk_vec<2, FDN_PRO_LN, 2, false, false, true>(d, s);
-                return launch_smallk_vec<2, FDN_PRO_NONE, 2, false, false, true>(d, s);
-            }
-        }
+        if (smallk_ok(d) && smallk_vec_ok(d)) return launch_smallk_vec_by_chunks<true>(d, s);
         return FDN_ERR_UNSUPPORTED;
     }
     {
@@ -1515,30 +1469,11 @@ extern "C" int fdn_conv1x1(const fdn_conv1x1_desc* dp, fdn_stream_t stream) {
         if (d.pro == FDN_PRO_LN) return nch == 3 ? launch_smallk_stream<3, FDN_PRO_LN>(d, s) : launch_smallk_stream<4, FDN_PRO_LN>(d, s);
         return nch == 3 ? launch_smallk_stream<3, FDN_PRO_NONE>(d, s) : launch_smallk_stream<4, FDN_PRO_NONE>(d, s);
     }
-    if (kstream_vec_ok(d)) {
-        const int tiles = (d.N + 31) / 32;
-        if (tiles == 1) return launch_kstream_vec<1>(d, s);
-        if (tiles == 2) return launch_kstream_vec<2>(d, s);
-        return launch_kstream_vec<3>(d, s);
-    }
-    if (narrow_vec_ok(d)) {
-        if (d.K <= KC) return launch_smallk_vec<1, FDN_PRO_NONE, 2, true>(d, s);
-        if (d.K <= 2 * KC) return launch_smallk_vec<2, FDN_PRO_NONE, 2, true>(d, s);
-        return launch_smallk_vec<3, FDN_PRO_NONE, 2, true>(d, s);
-    }
+    if (kstream_vec_ok(d)) return launch_kstream_by_tiles<false>(d, s);
+    if (narrow_vec_ok(d)) return launch_narrow_by_chunks<false>(d, s);
     if (smallk_ok(d) && smallk_vec_ok(d)) {
-        // measured (tools/bench_kernels.py to_hidden ffn_in, B=8 720p): 8-byte lanes win for K <= 32 (32->152: 1.65 -> 1.44 ms,
-        // 32->86: 0.92 -> 0.76 ms) and for K <= 64 while the weight matrix leaves room for 3 workgroups per CU (64->172:
-        // 0.74 -> 0.59 ms; 64->304 is slower vectorised); 16-byte lanes spill with the LN prologue
-        const int ntiles = (d.N + 31) / 32;
-        if (d.K <= KC) {
-            if (d.pro == FDN_PRO_LN) return launch_smallk_vec<1, FDN_PRO_LN, 2>(d, s);       // (16-byte lanes measure the same here)
-            return launch_smallk_vec<1, FDN_PRO_NONE, 2>(d, s);       // (8-byte lanes only: the kernel static_asserts VEC == 2)
-        }
-        if ((2UL * 2 * KC + 2UL * KC * (ntiles * 32 + 1)) * sizeof(float) <= 52 * 1024) {
-            if (d.pro == FDN_PRO_LN) return launch_smallk_vec<2, FDN_PRO_LN, 2>(d, s);
-            return launch_smallk_vec<2, FDN_PRO_NONE, 2>(d, s);
-        }
+        const int rc = launch_smallk_vec_by_chunks<false>(d, s);
+        if (rc != FDN_ERR_UNSUPPORTED) return rc;                  // (K > 32 with a wide weight matrix: the dword form below)
     }
     if (smallk_ok(d)) {
         switch (d.pro) {

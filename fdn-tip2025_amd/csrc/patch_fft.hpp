@@ -17,7 +17,7 @@ constexpr float C8 = 0.70710678118654752440f;
 // v_pk_add_f32, a multiplication by +-i a swizzle the compiler folds into op_sel / neg modifiers, a real scale one v_pk_mul_f32.
 // On gfx950 a wave64 v_pk_* instruction takes ~4.5 issue cycles against 4 for a scalar one (tools/micro/mfma_valu_coexec.hip), so
 // the packed forms cost a little over half the vector-ALU time of the component-wise ones (fft8: 37 instructions instead of 64).
-typedef float f2 __attribute__((ext_vector_type(2)));
+typedef fdn_f32x2 f2;
 __device__ __forceinline__ f2 mul_pi(f2 a) { return f2{-a.y, a.x}; }      // * (+i)
 __device__ __forceinline__ f2 mul_ni(f2 a) { return f2{a.y, -a.x}; }      // * (-i)
 __device__ __forceinline__ f2 cconj(f2 a) { return f2{a.x, -a.y}; }
@@ -147,21 +147,6 @@ __device__ __forceinline__ void fdsa_bin(float2 q, float2 k, float2 v, float f, 
 // buffer resources: per-lane byte offsets are computed once per workgroup (invalid lanes get an offset past
 // num_records, which loads as 0 and drops stores); the channel plane is a scalar offset, so walking planes
 // costs no vector ALU work (these kernels are VALU-issue bound, not HBM bound)
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr unsigned OOB = 0x80000000u;       // images are limited to < 2 GB per tensor so that OOB (+ small immediates) stays out of range
-__device__ __forceinline__ rsrc_t mk_rsrc(const float* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ float bload(rsrc_t r, unsigned voff, unsigned soff) {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ void bstore8(const float (&v)[8], rsrc_t r, unsigned voff, unsigned soff) {
-    u32x4 a, b;
-    a.x = __float_as_uint(v[0]); a.y = __float_as_uint(v[1]); a.z = __float_as_uint(v[2]); a.w = __float_as_uint(v[3]);
-    b.x = __float_as_uint(v[4]); b.y = __float_as_uint(v[5]); b.z = __float_as_uint(v[6]); b.w = __float_as_uint(v[7]);
-    __builtin_amdgcn_raw_buffer_store_b128(a, r, voff, soff, 0);
-    __builtin_amdgcn_raw_buffer_store_b128(b, r, voff + 16u, soff, 0);
-}
+// (rsrc_t, mk_rsrc, OOB, bload, bstore8: buffer_io.hpp)
 
 }  // namespace

@@ -46,11 +46,7 @@ __device__ __forceinline__ void halo_stash(float* t, const int (&slot)[HPT], con
 // 16-byte-lane form of the halo fetch (W % 4 == 0, 16-byte aligned planes): the 64 interior columns of the TH+2 rows
 // travel as float4 (3 per thread), the two edge columns as dwords (threads 0..2(TH+2)-1): 4 load instructions per plane
 // instead of 9, and a wave touches 1 KB contiguous
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 bload4(rsrc_t r, unsigned voff, unsigned soff) {
-    const u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
-    return f32x4{__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w)};
-}
+using f32x4 = fdn_f32x4;
 struct HaloV4 {
     unsigned g4[3], ge;      // global byte offsets (OOB when outside the image / past the tile)
     int s4[3], se;           // LDS slots (spare cells when past the tile)
@@ -569,7 +565,7 @@ constexpr int FNS = (FHP + 31) / 32;               // 11 strips of 32 pixels
 constexpr int FRS = 35;                            // LDS row stride of a hidden plane: (35 r + 8 px) mod 32 distinct for r < 8, px < 4
 constexpr int FPL = FHH * FRS;                     // floats per plane
 constexpr int FEG = 8;                             // channels per chunk (x 4 kinds = 32 MFMA rows)
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using f32x16 = fdn_f32x16;
 
 struct FusedArgs {
     const float* x;
