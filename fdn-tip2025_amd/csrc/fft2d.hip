@@ -14,10 +14,6 @@
 // values on the axes (so DC/Nyquist bins of real data stay exactly real).
 #include <math.h>
 
-#include <map>
-#include <mutex>
-#include <vector>
-
 #include "common.hpp"
 #include "fft_regs.hpp"
 
@@ -26,6 +22,7 @@ namespace {
 constexpr int MAX_STAGES = FDN_FFT_MAX_STAGES;    // fdn_fft_route reports up to this many stages
 constexpr int NT = 256;
 
+// (Plan and Rader are kernel arguments; the host code that fills them is fft_plan.hpp)
 struct Plan {
     int N;                     // transform length
     int nst;
@@ -33,69 +30,6 @@ struct Plan {
     const float2* tw;          // W_tabN^t, t in [0, tabN)
     int tab_mul;               // tabN / N
 };
-
-// ------------------------------------------------------------------------------------------
-// host: plan cache
-// ------------------------------------------------------------------------------------------
-std::mutex g_mu;
-std::map<std::pair<int, int>, const float2*> g_tables;   // (device, N) -> device table
-
-const float2* get_table(int N) {
-    int devid = 0;
-    if (hipGetDevice(&devid) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_tables.find({devid, N});
-    if (it != g_tables.end()) return it->second;
-    std::vector<float2> h(N);
-    for (int t = 0; t < N; ++t) {
-        double c, s;
-        if ((4L * t) % N == 0) {                      // exact on the axes
-            const int q = (int)((4L * t) / N);        // quarter turns
-            c = (q == 0) ? 1.0 : (q == 2 ? -1.0 : 0.0);
-            s = (q == 1) ? 1.0 : (q == 3 ? -1.0 : 0.0);
-        } else {
-            const double a = 2.0 * M_PI * (double)t / (double)N;
-            c = cos(a);
-            s = sin(a);
-        }
-        h[t] = make_float2((float)c, (float)(-s) + 0.0f);   // e^{-2 pi i t / N}; "+0" keeps zeros positive
-        if (h[t].y == 0.0f) h[t].y = 0.0f;
-        if (h[t].x == 0.0f) h[t].x = 0.0f;
-    }
-    float2* d = nullptr;
-    if (hipMalloc(&d, sizeof(float2) * N) != hipSuccess) return nullptr;
-    if (hipMemcpy(d, h.data(), sizeof(float2) * N, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    g_tables[{devid, N}] = d;
-    return d;
-}
-
-// the radix decomposition alone (host arithmetic, no table): what make_plan runs and what fdn_fft_route reports
-bool plan_radices(int N, Plan* p) {
-    p->N = N;
-    p->nst = 0;
-    p->tw = nullptr;
-    p->tab_mul = 0;
-    int n = N;
-    auto push = [&](int r) { if (p->nst < MAX_STAGES) p->radix[p->nst++] = r; };
-    int n2 = n, odd[MAX_STAGES], nodd = 0;
-    while (n2 % 2 == 0) n2 /= 2;
-    for (int f = 3; (long)f * f <= n2; f += 2)
-        while (n2 % f == 0) { if (nodd < MAX_STAGES) odd[nodd++] = f; n2 /= f; }
-    if (n2 > 1 && nodd < MAX_STAGES) odd[nodd++] = n2;
-    for (int i = nodd - 1; i >= 0; --i) { push(odd[i]); n /= odd[i]; }     // largest odd prime first
-    while (n % 4 == 0) { push(4); n /= 4; }
-    while (n % 2 == 0) { push(2); n /= 2; }
-    int prod = 1;
-    for (int i = 0; i < p->nst; ++i) prod *= p->radix[i];
-    return prod == N;
-}
-
-bool make_plan(int N, int tabN, Plan* p) {
-    if (!plan_radices(N, p) || tabN % N != 0) return false;
-    p->tw = get_table(tabN);
-    p->tab_mul = tabN / N;
-    return p->tw != nullptr;
-}
 
 // Rader's algorithm for a prime length p whose p-1 factors into the radices above (641 = W/2 of the
 // (W+2)-wide maps of fourier_fuse at 720p, FDN_arch.py:126,139): with a primitive root g,
@@ -109,86 +43,6 @@ struct Rader {
     const float2* bhat;        // [p-1]  FFT_{p-1}(b) / (p-1)
     Plan sub;                  // length p-1, its own table (tab_mul 1)
 };
-std::map<std::pair<int, int>, Rader> g_rader;
-
-bool is_prime(int n) {
-    if (n < 2) return false;
-    for (int f = 2; (long)f * f <= n; ++f)
-        if (n % f == 0) return false;
-    return true;
-}
-
-// radices with a register butterfly at every BIG >= 1 tier of fft_pass and a case in fft_run_inplace: the in-place column passes and
-// the Rader sub-transforms take only these
-bool reg_radix(int R) { return R == 2 || R == 3 || R == 4 || R == 5 || R == 7 || R == 17 || R == 23; }
-
-// Rader applies to p: a prime >= 29 whose p-1 factors into reg_radix radices (sub = that plan's radices, no table)
-bool rader_ok(int p, Plan* sub) {
-    if (p < 29 || !is_prime(p) || !plan_radices(p - 1, sub)) return false;
-    for (int i = 0; i < sub->nst; ++i)
-        if (!reg_radix(sub->radix[i])) return false;
-    return true;
-}
-
-// returns false when p is not prime / p-1 needs a radix without a register butterfly (caller keeps the gather pass)
-bool get_rader(int p, Rader* out) {
-    int devid = 0;
-    if (hipGetDevice(&devid) != hipSuccess) return false;
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        auto it = g_rader.find({devid, p});
-        if (it != g_rader.end()) { *out = it->second; return out->p != 0; }
-    }
-    Rader r = {};
-    auto fail = [&]() { std::lock_guard<std::mutex> lk(g_mu); g_rader[{devid, p}] = Rader{}; return false; };
-    if (!rader_ok(p, &r.sub)) return fail();
-    const int n = p - 1;
-    if (!make_plan(n, n, &r.sub)) return fail();
-    auto powmod = [&](long b, long e) { long x = 1; b %= p; while (e) { if (e & 1) x = x * b % p; b = b * b % p; e >>= 1; } return x; };
-    int g = 0;
-    for (int c = 2; c < p && !g; ++c) {
-        bool ok = true;
-        int m = n;
-        for (int f = 2; f <= m && ok; ++f)
-            if (m % f == 0) { if (powmod(c, n / f) == 1) ok = false; while (m % f == 0) m /= f; }
-        if (ok) g = c;
-    }
-    if (!g) return fail();
-    const long ginv = powmod(g, p - 2);
-    std::vector<int> pin(n), pout(n);
-    long a = 1, b = 1;
-    for (int q = 0; q < n; ++q) { pin[q] = (int)a; pout[q] = (int)b; a = a * g % p; b = b * ginv % p; }
-    std::vector<double> br(n), bi(n);
-    for (int m = 0; m < n; ++m) {                     // b[m] = w^(g^-m)
-        const double ang = -2.0 * M_PI * (double)pout[m] / (double)p;
-        br[m] = cos(ang); bi[m] = sin(ang);
-    }
-    std::vector<float2> bh(n);
-    for (int k = 0; k < n; ++k) {                     // plain DFT in double: n^2 = 4e5 terms, once per (device, p)
-        double sr = 0, si = 0;
-        for (int m = 0; m < n; ++m) {
-            const double ang = -2.0 * M_PI * (double)((long)k * m % n) / (double)n;
-            const double c = cos(ang), sn = sin(ang);
-            sr += br[m] * c - bi[m] * sn;
-            si += br[m] * sn + bi[m] * c;
-        }
-        bh[k] = make_float2((float)(sr / n), (float)(si / n));
-    }
-    int *dpi = nullptr, *dpo = nullptr;
-    float2* dbh = nullptr;
-    if (hipMalloc(&dpi, sizeof(int) * n) != hipSuccess || hipMalloc(&dpo, sizeof(int) * n) != hipSuccess ||
-        hipMalloc(&dbh, sizeof(float2) * n) != hipSuccess)
-        return fail();
-    if (hipMemcpy(dpi, pin.data(), sizeof(int) * n, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dpo, pout.data(), sizeof(int) * n, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dbh, bh.data(), sizeof(float2) * n, hipMemcpyHostToDevice) != hipSuccess)
-        return fail();
-    r.p = p; r.perm_in = dpi; r.perm_out = dpo; r.bhat = dbh;
-    std::lock_guard<std::mutex> lk(g_mu);
-    g_rader[{devid, p}] = r;
-    *out = r;
-    return true;
-}
 
 // ------------------------------------------------------------------------------------------
 // device: Stockham passes over sequences held in LDS
@@ -1090,221 +944,6 @@ __global__ __launch_bounds__((ColPlan<R, P>::NT), (3 * ColPlan<R, P>::lds <= 160
     }
 }
 
-// transposed twiddles of the R x P split: tab[n2 * R + k1] = W_H^{n2 k1}, exact on the axes
-const float2* get_table_rp(int R, int P) {
-    int devid = 0;
-    if (hipGetDevice(&devid) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> lk(g_mu);
-    const int key = -(R * 1024 + P);
-    auto it = g_tables.find({devid, key});
-    if (it != g_tables.end()) return it->second;
-    const int H = R * P;
-    std::vector<float2> h((size_t)R * P);
-    for (int n2 = 0; n2 < P; ++n2)
-        for (int k1 = 0; k1 < R; ++k1) {
-            const long t = ((long)n2 * k1) % H;
-            double c, s;
-            if ((4 * t) % H == 0) {
-                const int q = (int)((4 * t) / H);
-                c = (q == 0) ? 1.0 : (q == 2 ? -1.0 : 0.0);
-                s = (q == 1) ? 1.0 : (q == 3 ? -1.0 : 0.0);
-            } else {
-                const double ang = 2.0 * M_PI * (double)t / (double)H;
-                c = cos(ang); s = sin(ang);
-            }
-            float2 w = make_float2((float)c, (float)(-s) + 0.0f);
-            if (w.y == 0.0f) w.y = 0.0f;
-            if (w.x == 0.0f) w.x = 0.0f;
-            h[(size_t)n2 * R + k1] = w;
-        }
-    float2* d = nullptr;
-    if (hipMalloc(&d, sizeof(float2) * h.size()) != hipSuccess) return nullptr;
-    if (hipMemcpy(d, h.data(), sizeof(float2) * h.size(), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    g_tables[{devid, key}] = d;
-    return d;
-}
-
-template <int R, int P, int MODE>
-int launch_cols_rp(ColArgs a, long planes, fdn_stream_t stream) {
-    const float2* tw = get_table_rp(R, P);
-    if (!tw) return FDN_ERR_LAUNCH;
-    a.planes = planes;
-    if (a.C <= 0 || planes % a.C != 0) a.C = 1;
-    constexpr int TC = 256 / P;
-    const long total = (long)cdiv(a.Wf, TC) * planes, per_xcd = (total + 7) / 8;
-    if (per_xcd * 8 > 0x7FFFFFFFL) return FDN_ERR_UNSUPPORTED;
-    typedef ColPlan<R, P> CP;
-    constexpr size_t lds = CP::lds;
-    constexpr int nt = CP::NT;
-    if (int e = set_lds(fft_cols_rp_kernel<R, P, MODE>, lds)) return e;
-    hipLaunchKernelGGL((fft_cols_rp_kernel<R, P, MODE>), dim3((unsigned)(per_xcd * 8)), dim3(nt), lds, static_cast<hipStream_t>(stream), a, tw);
-    return fdn_launch_status();
-}
-
-// the compile-time plans: H = 23 * {32, 16, 8} (720p pyramid), 17 * {32, 16, 8} (1080p levels 2, 3 and 544-row inputs), 34 * 32
-// (1088 rows: 1080p level 1), and the shapes the reference's own drivers feed: LOL-Blur frames 640 x 1120
-// (inference_fdn_lolblur.py:16-17, already x32) and LOL-v1 400 x 600 padded to 416 x 608 (inference_fdn_lolv1.py:52-64)
-bool cols_plan(int H, int* R, int* P) {
-    for (int r : {23, 17, 20, 13})
-        for (int p : {32, 16, 8})
-            if (H == r * p) { *R = r; *P = p; return true; }
-    if (H == 34 * 32) { *R = 34; *P = 32; return true; }
-    return false;
-}
-
-template <int MODE>
-int launch_cols_planned(const ColArgs& a, long planes, fdn_stream_t stream, bool* done) {
-    int R = 0, P = 0;
-    *done = cols_plan(a.H, &R, &P);
-    if (!*done) return FDN_OK;
-    switch (R * 64 + P) {
-        case 23 * 64 + 32: return launch_cols_rp<23, 32, MODE>(a, planes, stream);
-        case 23 * 64 + 16: return launch_cols_rp<23, 16, MODE>(a, planes, stream);
-        case 23 * 64 + 8: return launch_cols_rp<23, 8, MODE>(a, planes, stream);
-        case 17 * 64 + 32: return launch_cols_rp<17, 32, MODE>(a, planes, stream);
-        case 17 * 64 + 16: return launch_cols_rp<17, 16, MODE>(a, planes, stream);
-        case 17 * 64 + 8: return launch_cols_rp<17, 8, MODE>(a, planes, stream);
-        case 34 * 64 + 32: return launch_cols_rp<34, 32, MODE>(a, planes, stream);
-        case 20 * 64 + 32: return launch_cols_rp<20, 32, MODE>(a, planes, stream);
-        case 20 * 64 + 16: return launch_cols_rp<20, 16, MODE>(a, planes, stream);
-        case 20 * 64 + 8: return launch_cols_rp<20, 8, MODE>(a, planes, stream);
-        case 13 * 64 + 32: return launch_cols_rp<13, 32, MODE>(a, planes, stream);
-        case 13 * 64 + 16: return launch_cols_rp<13, 16, MODE>(a, planes, stream);
-        case 13 * 64 + 8: return launch_cols_rp<13, 8, MODE>(a, planes, stream);
-        default: return FDN_ERR_UNSUPPORTED;                 // cols_plan lists a length this switch lacks
-    }
-}
-
-bool plan_big(const Plan& p) {
-    for (int i = 0; i < p.nst; ++i)
-        if (p.radix[i] == 17 || p.radix[i] == 23) return true;
-    return false;
-}
-bool plan_big2(const Plan& p) {
-    for (int i = 0; i < p.nst; ++i)
-        if (p.radix[i] == 13 || p.radix[i] == 37 || p.radix[i] == 41) return true;
-    return false;
-}
-
-int pick_tc(int H) {
-    const long per_col = 2L * H * sizeof(float2);
-    if (per_col * 16 <= 56 * 1024) return 16;
-    if (per_col * 8 <= 140 * 1024) return 8;
-    if (per_col * 4 <= 140 * 1024) return 4;
-    if (per_col * 2 <= 140 * 1024) return 2;
-    return 0;
-}
-
-
-int pick_rpb(int M) {
-    // rows per workgroup from an LDS budget for the ping-pong buffers.  Swept on the B=8 720p forward (row kernels, ms per
-    // step r2c / c2r): 16 KiB 16.6 / 15.0, 24 KiB 13.3 / 13.4, 32 KiB 13.3 / 12.0, 40 KiB 14.0 / 13.4, 48 KiB 14.1 / 13.4,
-    // 64 KiB 15.4 / 14.5 - the passes are latency bound, so workgroups per CU count for more than rows per workgroup
-    // (M = 640: 3 rows, 41 KiB with the tables, 3 workgroups per CU, 480 radix-4 jobs for 256 threads)
-    int rpb = (int)((32 * 1024) / (2L * M * sizeof(float2)));
-    if (rpb > 8) rpb = 8;
-    if (rpb < 1) rpb = 1;
-    return rpb;
-}
-
-// in-place passes possible: every radix has a register butterfly and its jobs fit NT*JMAX threads-slots
-int inplace_tc(const Plan& p, int H) {
-    for (int tc = 32; tc >= 8; tc >>= 1) {
-        if ((long)H * tc > (long)NT * 24) continue;               // keep the buffer <= 48 KiB: 3 workgroups per CU
-        bool ok = true;
-        for (int i = 0; i < p.nst && ok; ++i) {
-            const int R = p.radix[i];
-            if (!reg_radix(R)) ok = false;
-            else if ((long)(H / R) * tc > (long)NT * (EMAX / R)) ok = false;
-        }
-        if (ok) return tc;
-    }
-    return 0;
-}
-
-// The route a generic (not compile-time planned) length takes, decided on the host from the length alone.  The launchers and
-// fdn_fft_route both read it, so the query cannot drift from what runs.
-constexpr size_t LDS_MAX = 160 * 1024;        // per workgroup (gfx950)
-
-struct Route {
-    int kind;                  // FDN_FFT_REFUSED / _PLANNED / _INPLACE / _PINGPONG / _RADER (include/fdn_hip.h)
-    int big;                   // BIG of the kernel instantiation
-    int width;                 // columns per workgroup (tc) / rows per workgroup (rpb)
-    Plan p;                    // radices only (no table)
-    Plan sub;                  // FDN_FFT_RADER: the length p-1 sub-plan
-    size_t lds;
-};
-
-// columns of length H: in-place passes if every radix has an in-place butterfly and fits, else ping-pong passes with pick_tc
-// columns per workgroup; refused when no tc fits or the buffers plus the twiddle table exceed the LDS of a workgroup
-void cols_route(int H, Route* r) {
-    *r = Route{};
-    if (!plan_radices(H, &r->p)) return;
-    const int itc = inplace_tc(r->p, H);
-    if (itc > 0) {
-        r->kind = FDN_FFT_INPLACE;
-        r->width = itc;
-        r->big = plan_big(r->p) ? 1 : 0;
-        r->lds = ((size_t)H * itc + H) * sizeof(float2);
-        return;
-    }
-    const int tc = pick_tc(H);
-    const size_t lds = (2UL * H * tc + H) * sizeof(float2);
-    if (tc == 0 || lds > LDS_MAX) return;
-    r->kind = FDN_FFT_PINGPONG;
-    r->width = tc;
-    r->big = plan_big2(r->p) ? 2 : plan_big(r->p) ? 1 : 0;
-    r->lds = lds;
-}
-
-// rows of width W (half-length M = W / 2) on the generic kernels: Stockham passes, or (forward only) Rader for a prime M;
-// refused when the ping-pong rows, the table and the Rader scratch exceed the LDS of a workgroup
-void rows_route(int W, bool fwd, Route* r) {
-    *r = Route{};
-    const int M = W / 2;
-    if (!plan_radices(M, &r->p)) return;
-    const bool rader = fwd && r->p.nst == 1 && rader_ok(M, &r->sub);   // prime half-length: convolution form instead of the O(N^2) gather
-    const int rpb = pick_rpb(M);
-    const size_t lds = (2UL * rpb * M + W + (rader ? (size_t)M + rpb : 0)) * sizeof(float2);
-    if (lds > LDS_MAX) return;
-    r->kind = rader ? FDN_FFT_RADER : FDN_FFT_PINGPONG;
-    r->width = rpb;
-    r->big = (plan_big(r->p) || (rader && plan_big(r->sub))) ? 1 : 0;
-    r->lds = lds;
-}
-
-template <int MODE, int BIG, bool INPL>
-int launch_cols_k(ColArgs a, const Plan& p, long planes, size_t lds, fdn_stream_t stream) {
-    a.planes = planes;
-    if (a.C <= 0 || planes % a.C != 0) a.C = 1;
-    if (int e = set_lds(fft_cols_kernel<MODE, BIG, INPL>, lds)) return e;
-    const long total = (long)cdiv(a.Wf, a.tc) * planes, per_xcd = (total + 7) / 8;
-    if (per_xcd * 8 > 0x7FFFFFFFL) return FDN_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((fft_cols_kernel<MODE, BIG, INPL>), dim3((unsigned)(per_xcd * 8)), dim3(NT), lds,
-                       static_cast<hipStream_t>(stream), a, p);
-    return fdn_launch_status();
-}
-
-template <int MODE>
-int launch_cols(ColArgs a, long planes, fdn_stream_t stream) {
-    {
-        bool done = false;
-        const int e = launch_cols_planned<MODE>(a, planes, stream, &done);
-        if (done) return e;
-    }
-    Route r;
-    cols_route(a.H, &r);
-    if (r.kind == FDN_FFT_REFUSED) return FDN_ERR_UNSUPPORTED;
-    Plan p;
-    if (!make_plan(a.H, a.H, &p)) return FDN_ERR_UNSUPPORTED;
-    a.tc = r.width;
-    a.tcs = __builtin_ctz(r.width);
-    if (r.kind == FDN_FFT_INPLACE)
-        return r.big ? launch_cols_k<MODE, 1, true>(a, p, planes, r.lds, stream) : launch_cols_k<MODE, 0, true>(a, p, planes, r.lds, stream);
-    if (r.big == 2) return launch_cols_k<MODE, 2, false>(a, p, planes, r.lds, stream);
-    return r.big ? launch_cols_k<MODE, 1, false>(a, p, planes, r.lds, stream) : launch_cols_k<MODE, 0, false>(a, p, planes, r.lds, stream);
-}
-
 // ------------------------------------------------------------------------------------------
 // Rows with a compile-time plan: half-length M = R1 * P with R1 = 20 (720p: W = 1280 / 640 / 320) or 30 (1080p: 1920 /
 // 960 / 480) and P = 32 / 16 / 8.  Same scheme as the planned columns: thread (n2, row) runs the R1-point DFT over n1 on
@@ -1543,40 +1182,60 @@ __global__ __launch_bounds__(256, 2) void irfft_rows_rp_kernel(const float2* __r
     }
 }
 
-// [ (P-1) * R1 transposed twiddles W_M^{n2 k1} | M + 1 split twiddles W_W^k ], exact on the axes
-const float2* get_table_rows_rp(int R1, int P) {
-    int devid = 0;
-    if (hipGetDevice(&devid) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> lk(g_mu);
-    const int key = -(1 << 24) - (R1 * 1024 + P);
-    auto it = g_tables.find({devid, key});
-    if (it != g_tables.end()) return it->second;
-    const int M = R1 * P, W = 2 * M;
-    auto root = [](long t, long N) {
-        t %= N;
-        double c, s;
-        if ((4 * t) % N == 0) {
-            const int q = (int)((4 * t) / N);
-            c = (q == 0) ? 1.0 : (q == 2 ? -1.0 : 0.0);
-            s = (q == 1) ? 1.0 : (q == 3 ? -1.0 : 0.0);
-        } else {
-            const double ang = 2.0 * M_PI * (double)t / (double)N;
-            c = cos(ang); s = sin(ang);
-        }
-        float2 w = make_float2((float)c, (float)(-s) + 0.0f);
-        if (w.y == 0.0f) w.y = 0.0f;
-        if (w.x == 0.0f) w.x = 0.0f;
-        return w;
-    };
-    std::vector<float2> h;
-    for (int n2 = 1; n2 < P; ++n2)
-        for (int k1 = 0; k1 < R1; ++k1) h.push_back(root((long)n2 * k1, M));
-    for (int k = 0; k <= M; ++k) h.push_back(root(k, W));
-    float2* d = nullptr;
-    if (hipMalloc(&d, sizeof(float2) * h.size()) != hipSuccess) return nullptr;
-    if (hipMemcpy(d, h.data(), sizeof(float2) * h.size(), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    g_tables[{devid, key}] = d;
-    return d;
+}  // namespace
+
+#include "fft_plan.hpp"
+
+// ------------------------------------------------------------------------------------------
+// launch side: every launcher reads the Route of its length (fft_plan.hpp) and nothing else decides which kernel runs
+// ------------------------------------------------------------------------------------------
+namespace {
+
+template <int R, int P, int MODE>
+int launch_cols_rp(ColArgs a, long planes, fdn_stream_t stream) {
+    const float2* tw = get_table_rp(R, P);
+    if (!tw) return FDN_ERR_LAUNCH;
+    a.planes = planes;
+    if (a.C <= 0 || planes % a.C != 0) a.C = 1;
+    constexpr int TC = 256 / P;
+    const long total = (long)cdiv(a.Wf, TC) * planes, per_xcd = (total + 7) / 8;
+    if (per_xcd * 8 > 0x7FFFFFFFL) return FDN_ERR_UNSUPPORTED;
+    typedef ColPlan<R, P> CP;
+    constexpr size_t lds = CP::lds;
+    constexpr int nt = CP::NT;
+    if (int e = set_lds(fft_cols_rp_kernel<R, P, MODE>, lds)) return e;
+    hipLaunchKernelGGL((fft_cols_rp_kernel<R, P, MODE>), dim3((unsigned)(per_xcd * 8)), dim3(nt), lds, static_cast<hipStream_t>(stream), a, tw);
+    return fdn_launch_status();
+}
+
+template <int MODE, int BIG, bool INPL>
+int launch_cols_k(ColArgs a, const Plan& p, long planes, size_t lds, fdn_stream_t stream) {
+    a.planes = planes;
+    if (a.C <= 0 || planes % a.C != 0) a.C = 1;
+    if (int e = set_lds(fft_cols_kernel<MODE, BIG, INPL>, lds)) return e;
+    const long total = (long)cdiv(a.Wf, a.tc) * planes, per_xcd = (total + 7) / 8;
+    if (per_xcd * 8 > 0x7FFFFFFFL) return FDN_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL((fft_cols_kernel<MODE, BIG, INPL>), dim3((unsigned)(per_xcd * 8)), dim3(NT), lds,
+                       static_cast<hipStream_t>(stream), a, p);
+    return fdn_launch_status();
+}
+
+template <int MODE>
+int launch_cols(ColArgs a, long planes, fdn_stream_t stream) {
+    Route r;
+    cols_route(a.H, &r);
+    if (r.kind == FDN_FFT_REFUSED) return FDN_ERR_UNSUPPORTED;
+    if (r.kind == FDN_FFT_PLANNED)
+        return col_plan(a.H, [&](auto R, auto P) { return launch_cols_rp<decltype(R)::value, decltype(P)::value, MODE>(a, planes, stream); });
+    Plan p;
+    if (!make_plan(a.H, a.H, &p)) return FDN_ERR_UNSUPPORTED;
+    a.tc = r.width;
+    a.tcs = __builtin_ctz(r.width);
+    // (BIG, INPL) of fft_cols_kernel as 4 * INPL + BIG: the in-place passes exist at BIG 0 / 1, the ping-pong passes at 0 / 1 / 2
+    return dispatch<0, 1, 2, 4 + 0, 4 + 1>(4 * (r.kind == FDN_FFT_INPLACE) + r.big, [&](auto v) {
+        constexpr int V = decltype(v)::value;
+        return launch_cols_k<MODE, V % 4, V / 4 != 0>(a, p, planes, r.lds, stream);
+    });
 }
 
 template <int R1, int P>
@@ -1584,16 +1243,13 @@ int launch_rfft_rp(const float* in, float* out_c, long rows, fdn_stream_t stream
     typedef RowPlan<R1, P> L;
     const float2* tab = get_table_rows_rp(R1, P);
     if (!tab) return FDN_ERR_LAUNCH;
-    if (ln) {
-        if (int e = set_lds(rfft_rows_rp_kernel<R1, P, true>, L::lds)) return e;
-        hipLaunchKernelGGL((rfft_rows_rp_kernel<R1, P, true>), dim3(cdiv(rows, L::RW)), dim3(256), L::lds, static_cast<hipStream_t>(stream),
-                           in, reinterpret_cast<float2*>(out_c), rows, tab, *ln, pitch);
+    return dispatch<0, 1>(ln != nullptr, [&](auto v) {
+        constexpr bool LN = decltype(v)::value != 0;
+        if (int e = set_lds(rfft_rows_rp_kernel<R1, P, LN>, L::lds)) return e;
+        hipLaunchKernelGGL((rfft_rows_rp_kernel<R1, P, LN>), dim3(cdiv(rows, L::RW)), dim3(256), L::lds, static_cast<hipStream_t>(stream), in,
+                           reinterpret_cast<float2*>(out_c), rows, tab, ln ? *ln : RowLN{}, pitch);
         return fdn_launch_status();
-    }
-    if (int e = set_lds(rfft_rows_rp_kernel<R1, P, false>, L::lds)) return e;
-    hipLaunchKernelGGL((rfft_rows_rp_kernel<R1, P, false>), dim3(cdiv(rows, L::RW)), dim3(256), L::lds, static_cast<hipStream_t>(stream), in,
-                       reinterpret_cast<float2*>(out_c), rows, tab, RowLN{}, pitch);
-    return fdn_launch_status();
+    });
 }
 
 template <int R1, int P>
@@ -1609,64 +1265,24 @@ int launch_irfft_rp(const float* in_c, long in_row_bins, long in_plane_bins, flo
     return fdn_launch_status();
 }
 
-// W -> (R1, P) of the planned row kernels; 0 = none
-bool rows_plan(int W, int* R1, int* P) {
-    for (int r : {20, 30})
-        for (int p : {32, 16, 8})
-            if (W == 2 * r * p) { *R1 = r; *P = p; return true; }
-    for (int p : {16, 8})                                   // LOL-v1 padded: W = 608 / 304 (19 x 16, 19 x 8; 152 = 2 x 19 x 4 stays generic)
-        if (W == 2 * 19 * p) { *R1 = 19; *P = p; return true; }
-    for (int p : {16, 8, 4})                                // LOL-Blur frames (inference_fdn_lolblur.py:16-17): W = 1120 / 560 / 280
-        if (W == 2 * 35 * p) { *R1 = 35; *P = p; return true; }
-    return false;
-}
-#define FDN_ROWS_DISPATCH(CALL)                                        \
-    switch (R1 * 64 + P) {                                             \
-        case 20 * 64 + 32: return CALL(20, 32);                        \
-        case 20 * 64 + 16: return CALL(20, 16);                        \
-        case 20 * 64 + 8: return CALL(20, 8);                          \
-        case 30 * 64 + 32: return CALL(30, 32);                        \
-        case 30 * 64 + 16: return CALL(30, 16);                        \
-        case 30 * 64 + 8: return CALL(30, 8);                          \
-        case 19 * 64 + 16: return CALL(19, 16);                        \
-        case 19 * 64 + 8: return CALL(19, 8);                          \
-        case 35 * 64 + 16: return CALL(35, 16);                        \
-        case 35 * 64 + 8: return CALL(35, 8);                          \
-        case 35 * 64 + 4: return CALL(35, 4);                          \
-        default: break;                                                \
-    }
-
 }  // namespace
 
 extern "C" int fdn_fft_prepare(int n) {
     FDN_CHECK_ARG(n > 0);
-    {
-        int R = 0, P = 0;                                                       // column lengths with a compile-time plan
-        if (cols_plan(n, &R, &P) && !get_table_rp(R, P)) return FDN_ERR_LAUNCH;
-    }
-    {
-        int R1 = 0, P = 0;                                                      // row widths with a compile-time plan
-        if (rows_plan(n, &R1, &P) && !get_table_rows_rp(R1, P)) return FDN_ERR_LAUNCH;
-    }
-    return get_table(n) ? FDN_OK : FDN_ERR_LAUNCH;
+    const auto made = [](const float2* tab) { return tab ? FDN_OK : FDN_ERR_LAUNCH; };
+    // the tables of a compile-time plan, if n is a planned column length / row width
+    if (col_plan(n, [&](auto R, auto P) { return made(get_table_rp(R, P)); }) == FDN_ERR_LAUNCH) return FDN_ERR_LAUNCH;
+    if (row_plan(n, [&](auto R1, auto P) { return made(get_table_rows_rp(R1, P)); }) == FDN_ERR_LAUNCH) return FDN_ERR_LAUNCH;
+    return made(get_table(n));
 }
 
 extern "C" int fdn_fft_route(int kind, int n, int* desc, int ndesc) {
     FDN_CHECK_ARG(kind >= 0 && kind <= 2 && n >= 1 && desc && ndesc >= FDN_FFT_ROUTE_DESC);
     FDN_CHECK_ARG(kind == 2 || n % 2 == 0);                                    // the row launchers take even widths only
     for (int i = 0; i < FDN_FFT_ROUTE_DESC; ++i) desc[i] = 0;
-    int R = 0, P = 0;
-    if (kind == 2 ? cols_plan(n, &R, &P) : rows_plan(n, &R, &P)) {
-        desc[0] = FDN_FFT_PLANNED;
-        desc[2] = kind == 2 ? 256 / P : row_plan_groups(R, P) * (32 / P);    // columns / rows per workgroup
-        desc[4] = 2;
-        desc[5] = R;
-        desc[6] = P;
-        return FDN_OK;
-    }
     Route r;
     if (kind == 2) cols_route(n, &r);
-    else rows_route(n, kind == 0, &r);
+    else rows_route(n, kind == 0, true, &r);
     desc[0] = r.kind;
     if (r.kind == FDN_FFT_REFUSED) return FDN_OK;
     desc[1] = r.big;
@@ -1674,13 +1290,14 @@ extern "C" int fdn_fft_route(int kind, int n, int* desc, int ndesc) {
     const Plan& q = r.kind == FDN_FFT_RADER ? r.sub : r.p;
     desc[3] = r.kind == FDN_FFT_RADER ? n / 2 : 0;
     desc[4] = q.nst;
+    const bool passes = r.kind == FDN_FFT_PINGPONG || r.kind == FDN_FFT_RADER;   // the routes that run fft_pass
     for (int i = 0; i < q.nst; ++i) {
         const int x = q.radix[i];
         // fft_pass: register butterflies for 2 / 4 / 3 / 5 / 7, + 17 / 23 at BIG >= 1, + 13 / 37 / 41 at BIG == 2; any other radix gathers
         const bool reg = x == 2 || x == 4 || x == 3 || x == 5 || x == 7 || (r.big >= 1 && (x == 17 || x == 23)) ||
                          (r.big == 2 && (x == 13 || x == 37 || x == 41));
         desc[5 + i] = x;
-        desc[5 + MAX_STAGES + i] = (r.kind != FDN_FFT_INPLACE && !reg) ? 1 : 0;
+        desc[5 + MAX_STAGES + i] = (passes && !reg) ? 1 : 0;
     }
     return FDN_OK;
 }
@@ -1706,33 +1323,24 @@ extern "C" int fdn_sincos_f32(const float* x, float* sn, float* cs, long n, fdn_
 extern "C" int fdn_rfft_rows(const float* in, float* out_c, long rows, int W, long out_row_bins, fdn_stream_t stream) {
     FDN_CHECK_ARG(in && out_c && rows > 0 && W >= 2 && W % 2 == 0 && (out_row_bins == 0 || (out_row_bins >= W / 2 + 1 && out_row_bins < (1L << 20))));
     const int pitch = out_row_bins ? (int)out_row_bins : W / 2 + 1;
-    {
-        int R1 = 0, P = 0;
-        if (rows_plan(W, &R1, &P) && (reinterpret_cast<uintptr_t>(in) & 7) == 0) {
-#define FDN_CALL(a, b) launch_rfft_rp<a, b>(in, out_c, rows, stream, pitch)
-            FDN_ROWS_DISPATCH(FDN_CALL)
-#undef FDN_CALL
-        }
-    }
     Route r;
-    rows_route(W, true, &r);
+    rows_route(W, true, aligned8(in), &r);
     if (r.kind == FDN_FFT_REFUSED) return FDN_ERR_UNSUPPORTED;
+    if (r.kind == FDN_FFT_PLANNED)
+        return row_plan(W, [&](auto R1, auto P) { return launch_rfft_rp<decltype(R1)::value, decltype(P)::value>(in, out_c, rows, stream, pitch); });
     Plan p;
     if (!make_plan(W / 2, W, &p)) return FDN_ERR_UNSUPPORTED;
     Rader rd = {};
     if (r.kind == FDN_FFT_RADER && !get_rader(W / 2, &rd)) return FDN_ERR_LAUNCH;
     const int rpb = r.width;
     const size_t lds = r.lds;
-    if (r.big) {
-        if (int e = set_lds(rfft_rows_kernel<true>, lds)) return e;
-        hipLaunchKernelGGL(rfft_rows_kernel<true>, dim3(cdiv(rows, rpb)), dim3(NT), lds, static_cast<hipStream_t>(stream), in,
+    return dispatch<0, 1>(r.big, [&](auto v) {
+        constexpr bool BIG = decltype(v)::value != 0;
+        if (int e = set_lds(rfft_rows_kernel<BIG>, lds)) return e;
+        hipLaunchKernelGGL(rfft_rows_kernel<BIG>, dim3(cdiv(rows, rpb)), dim3(NT), lds, static_cast<hipStream_t>(stream), in,
                            reinterpret_cast<float2*>(out_c), W, rows, rpb, p, rd, pitch);
-    } else {
-        if (int e = set_lds(rfft_rows_kernel<false>, lds)) return e;
-        hipLaunchKernelGGL(rfft_rows_kernel<false>, dim3(cdiv(rows, rpb)), dim3(NT), lds, static_cast<hipStream_t>(stream), in,
-                           reinterpret_cast<float2*>(out_c), W, rows, rpb, p, rd, pitch);
-    }
-    return fdn_launch_status();
+        return fdn_launch_status();
+    });
 }
 
 extern "C" int fdn_rfft_rows_ln(const float* x, const float* stats, const float* gamma, const float* beta, float* out_c, int B, int C,
@@ -1741,50 +1349,40 @@ extern "C" int fdn_rfft_rows_ln(const float* x, const float* stats, const float*
     FDN_CHECK_ARG(out_row_bins == 0 || (out_row_bins >= W / 2 + 1 && out_row_bins < (1L << 20)));
     const int pitch = out_row_bins ? (int)out_row_bins : W / 2 + 1;
     FDN_CHECK_ARG((long)H * W < (1L << 28));
-    int R1 = 0, P = 0;
-    if (!rows_plan(W, &R1, &P) || (reinterpret_cast<uintptr_t>(x) & 7) != 0 || (reinterpret_cast<uintptr_t>(stats) & 7) != 0)
-        return FDN_ERR_UNSUPPORTED;                           // widths with a compile-time plan only: else fdn_layernorm_chan + fdn_rfft_rows
+    Route r;
+    rows_route(W, true, aligned8(x, stats), &r);
+    if (r.kind != FDN_FFT_PLANNED) return FDN_ERR_UNSUPPORTED;   // widths with a compile-time plan only: else fdn_layernorm_chan + fdn_rfft_rows
     if ((long)B * 2 * H * W * 4 > 0x7FFFFFFFL) return FDN_ERR_UNSUPPORTED;      // the statistics of all batch items sit behind one 2 GB descriptor
     const RowLN ln = {stats, gamma, beta, C, H};
     const long rows = (long)B * C * H;
-#define FDN_CALL(a, b) launch_rfft_rp<a, b>(x, out_c, rows, stream, pitch, &ln)
-    FDN_ROWS_DISPATCH(FDN_CALL)
-#undef FDN_CALL
-    return FDN_ERR_UNSUPPORTED;
+    return row_plan(W, [&](auto R1, auto P) { return launch_rfft_rp<decltype(R1)::value, decltype(P)::value>(x, out_c, rows, stream, pitch, &ln); });
 }
 
 extern "C" int fdn_irfft_rows(const float* in_c, long in_row_bins, long in_plane_bins, float* out, long planes, int H, int W,
                               float scale, const float* res, float alpha, fdn_stream_t stream) {
     FDN_CHECK_ARG(in_c && out && planes > 0 && H > 0 && W >= 2 && W % 2 == 0 && in_row_bins >= W / 2 + 1);
-    {
-        int R1 = 0, P = 0;
-        if (rows_plan(W, &R1, &P) && ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(res)) & 7) == 0) {
-#define FDN_CALL(a, b) launch_irfft_rp<a, b>(in_c, in_row_bins, in_plane_bins, out, planes, H, scale, res, alpha, stream)
-            FDN_ROWS_DISPATCH(FDN_CALL)
-#undef FDN_CALL
-        }
-    }
     Route r;
-    rows_route(W, false, &r);
+    rows_route(W, false, aligned8(out, res), &r);
     if (r.kind == FDN_FFT_REFUSED) return FDN_ERR_UNSUPPORTED;
+    if (r.kind == FDN_FFT_PLANNED)
+        return row_plan(W, [&](auto R1, auto P) {
+            return launch_irfft_rp<decltype(R1)::value, decltype(P)::value>(in_c, in_row_bins, in_plane_bins, out, planes, H, scale, res, alpha, stream);
+        });
     Plan p;
     if (!make_plan(W / 2, W, &p)) return FDN_ERR_UNSUPPORTED;
     const int rpb = r.width;
     const size_t lds = r.lds;
     const long rows = planes * H;
-    if (r.big) {
-        if (int e = set_lds(irfft_rows_kernel<true>, lds)) return e;
-        hipLaunchKernelGGL(irfft_rows_kernel<true>, dim3(cdiv(rows, rpb)), dim3(NT), lds, static_cast<hipStream_t>(stream),
+    return dispatch<0, 1>(r.big, [&](auto v) {
+        constexpr bool BIG = decltype(v)::value != 0;
+        if (int e = set_lds(irfft_rows_kernel<BIG>, lds)) return e;
+        hipLaunchKernelGGL(irfft_rows_kernel<BIG>, dim3(cdiv(rows, rpb)), dim3(NT), lds, static_cast<hipStream_t>(stream),
                            reinterpret_cast<const float2*>(in_c), in_row_bins, (long)H, in_plane_bins, out, W, H, rows, rpb,
                            scale, res, alpha, p);
-    } else {
-        if (int e = set_lds(irfft_rows_kernel<false>, lds)) return e;
-        hipLaunchKernelGGL(irfft_rows_kernel<false>, dim3(cdiv(rows, rpb)), dim3(NT), lds, static_cast<hipStream_t>(stream),
-                           reinterpret_cast<const float2*>(in_c), in_row_bins, (long)H, in_plane_bins, out, W, H, rows, rpb,
-                           scale, res, alpha, p);
-    }
-    return fdn_launch_status();
+        return fdn_launch_status();
+    });
 }
+
 
 __global__ __launch_bounds__(256) void pack_guidance_kernel(const float* __restrict__ amp, const float* __restrict__ pha,
                                                             float4* __restrict__ out, int H, int Wf, int pitch, long total) {

@@ -4,6 +4,7 @@ Inputs are fp32 ROCm tensors in NCHW layout.  A tensor argument may be a channel
 `t[:, a:b]` of a contiguous NCHW tensor (inner three dims dense, arbitrary batch stride).
 """
 import ctypes
+import functools
 
 import torch
 
@@ -519,18 +520,21 @@ def rfft_rows(x, pitch=None):
     return out
 
 
-ROWS_PLANNED_W = tuple(2 * r * p for r in (20, 30) for p in (32, 16, 8)) + (608, 304) + (1120, 560, 280)     # widths fdn_rfft_rows_ln has a form for (19 x 16, 19 x 8: LOL-v1 padded; 35 x 16 / 8 / 4: LOL-Blur frames)
+@functools.lru_cache(maxsize=None)
+def _rows_planned(W):
+    """The row kernels have a compile-time plan for width W (asked of the library once per width: rows_ln_ok runs per encoder block)."""
+    return W >= 2 and W % 2 == 0 and fft_route(FFT_ROWS, W)["route"] == "planned"
 
 
 def rows_ln_ok(x):
     """fdn_rfft_rows_ln has a form for this tensor: a planned width, and the statistics of the whole batch behind one 2 GB descriptor
     (fft2d.hip; a larger batch takes fdn_layernorm_chan + fdn_rfft_rows, as include/fdn_hip.h says)"""
     B, _, H, W = x.shape
-    return W in ROWS_PLANNED_W and B * 2 * H * W * 4 <= 0x7FFFFFFF
+    return _rows_planned(W) and B * 2 * H * W * 4 <= 0x7FFFFFFF
 
 
 def rfft_rows_ln(x, stats, gamma, beta, pitch=None):
-    """rfft along rows of the channel LayerNorm of x [B, C, H, W], normalised on load (fdn_rfft_rows_ln); W in ROWS_PLANNED_W."""
+    """rfft along rows of the channel LayerNorm of x [B, C, H, W], normalised on load (fdn_rfft_rows_ln); a planned width (rows_ln_ok)."""
     B, C, H, W = x.shape
     out = torch.empty((B, C, H, pitch or W // 2 + 1, 2), device=x.device, dtype=torch.float32)
     check(lib().fdn_rfft_rows_ln(_flat(x, "x"), _flat(stats, "stats"), _flat(gamma, "gamma"), _flat(beta, "beta"), _flat(out, "out"),

@@ -121,6 +121,10 @@ FFT_COL_ROUTES = {
     1: ("inplace", 0, 32, ()), 2: ("inplace", 0, 32, ()), 3: ("inplace", 0, 32, ()),
     4097: ("refused", 0, 0, ()), 4480: ("refused", 0, 0, ()), 4482: ("refused", 0, 0, ()),    # ping-pong buffers + table > 160 KiB of LDS
 }
+# the lengths with a compile-time plan (FDN_COL_PLANS / FDN_ROW_PLANS of csrc/fft_plan.hpp): the CPU suite checks that fdn_fft_route answers
+# "planned" for exactly these, tests/test_gpu_fft_planned.py runs each
+PLANNED_H = [736, 368, 184, 544, 272, 136, 1088, 640, 320, 160, 416, 208, 104]       # + the LOL-Blur (640 x 1120) and padded LOL-v1 (416 x 608) pyramids
+PLANNED_W = [1280, 640, 320, 1920, 960, 480, 608, 304, 1120, 560, 280]      # (35 x 16 / 8 / 4: 7 / 7 / 6 row groups per workgroup, a partly filled first stage)
 # rows, width W: (forward route, BIG, rpb, radices that run the gather pass, Rader prime)
 FFT_ROW_ROUTES = {
     160: ("pingpong", 0, 8, (), 0), 224: ("pingpong", 0, 8, (), 0), 352: ("pingpong", 0, 8, (11,), 0), 546: ("pingpong", 0, 7, (13,), 0),

@@ -439,7 +439,9 @@ def test_fft_route_pins_the_lengths_the_gpu_tests_use(lib):
 def test_fft_route_sweep_invariants(lib):
     """Every column length 1..4600 and every even row width 2..10260: the plan is a factorisation, an in-place plan uses only radices
     fft_run_inplace has a case for (at its BIG), register radices imply their BIG tier, a Rader sub-plan has no gather stage, tc / rpb
-    are within their bounds, and a length is refused exactly where the LDS of a workgroup (160 KiB) runs out."""
+    are within their bounds, and a length is refused exactly where the LDS of a workgroup (160 KiB) runs out.  The lengths answered
+    "planned" are exactly PLANNED_H / PLANNED_W (tests/common.py), each as its factors (R, P)."""
+    from common import PLANNED_H, PLANNED_W
     from fdn_hip import ops
     inplace = _kernel_switch("fft_run_inplace", "__device__ void fft_run_inplace(")
     reg = _kernel_switch("fft_pass", "__device__ void fft_pass(")
@@ -447,13 +449,19 @@ def test_fft_route_sweep_invariants(lib):
     assert set(inplace) >= {2, 3, 4, 5, 7}
     lds_max = 160 * 1024
     seen = set()
+    planned = {ops.FFT_COLS: set(), ops.FFT_ROWS: set(), ops.FFT_IROWS: set()}
     for kind, lengths in ((ops.FFT_COLS, range(1, 4601)), (ops.FFT_ROWS, range(2, 10262, 2)), (ops.FFT_IROWS, range(2, 10262, 2))):
         for n in lengths:
             rt = ops.fft_route(kind, n)
             seen.add((kind, rt["route"], rt["big"]))
-            if rt["route"] == "planned":
-                continue
             N = n if kind == ops.FFT_COLS else n // 2
+            if rt["route"] == "planned":
+                planned[kind].add(n)
+                R, P = rt["radices"]
+                assert R * P == N and (rt["big"], rt["rader"], rt["gather"]) == (0, 0, ()), (kind, n, rt)
+                if kind == ops.FFT_COLS:
+                    assert rt["width"] == 256 // P, (n, rt)
+                continue
             if kind == ops.FFT_COLS:
                 # no column length <= 4096 needs more than tc 2 of ping-pong buffers and the table; 4097 and up do
                 assert (rt["route"] == "refused") == (n > 4096), (n, rt)
@@ -492,10 +500,22 @@ def test_fft_route_sweep_invariants(lib):
             assert rt["big"] == want_big, (kind, n, rt)
             if rt["route"] != "inplace":
                 assert rt["gather"] == tuple(r for r in radices if reg.get(r, 99) > rt["big"]), (kind, n, rt)
+    assert planned[ops.FFT_COLS] == set(PLANNED_H) and len(PLANNED_H) == 13
+    assert planned[ops.FFT_ROWS] == set(PLANNED_W) and planned[ops.FFT_IROWS] == set(PLANNED_W) and len(PLANNED_W) == 11
     # every route and BIG tier the kernels have is reached by some length
     for want in [(2, "inplace", 0), (2, "inplace", 1), (2, "pingpong", 0), (2, "pingpong", 1), (2, "pingpong", 2), (2, "refused", 0),
                  (0, "pingpong", 0), (0, "pingpong", 1), (0, "rader", 0), (0, "rader", 1), (0, "refused", 0), (1, "pingpong", 0), (1, "pingpong", 1)]:
         assert want in seen, want
+
+
+def test_rows_ln_ok_follows_the_planned_widths(lib):
+    """ops.rows_ln_ok asks the library: true for a (1, 3, 8, W) tensor exactly when W has a compile-time plan (only .shape is read)."""
+    from common import PLANNED_W
+    from fdn_hip import ops
+    for W in range(2, 2049, 2):
+        assert ops.rows_ln_ok(torch.empty(1, 3, 8, W, device="meta")) == (W in PLANNED_W), W
+    assert not ops.rows_ln_ok(torch.empty(1, 3, 8, 641, device="meta"))                     # an odd width is no error here
+    assert not ops.rows_ln_ok(torch.empty(2 ** 20, 3, 8, 1280, device="meta"))              # statistics past 2 GB
 
 
 def test_fft_route_argument_validation(lib):
