@@ -3,6 +3,7 @@
 //                 (inference_fdn_lolblur.py:47-62, basicsr/utils/img_util.py:9-33)
 //   fdn_post_u8 : crop -> clamp(0,1) -> *255 -> round half-to-even -> uint8 HWC, RGB -> BGR
 //                 (inference_fdn_lolblur.py:72-75, basicsr/utils/img_util.py:36-98)
+//   fdn_tiles_gather_u8 / fdn_tiles_merge_u8 : the tiled path's pair between a uint8 frame and fp32 tiles (ABI 21)
 // Pure byte <-> float reshuffles, HBM-bound: a thread owns one pixel (3 bytes in, 3 coalesced plane
 // stores out, or the reverse).
 #include "common.hpp"
@@ -71,6 +72,55 @@ __global__ __launch_bounds__(256) void tiles_merge_kernel(const float* __restric
     out[(long)c * H * W + px] = acc / cnt;
 }
 
+// The same pair between a uint8 HWC frame and fp32 tiles, without the frame-sized fp32 image in between: gather = pre_u8_kernel's
+// /255 and channel order (no padding: tiles are cut from the frame itself) + tiles_gather_kernel's indexing; merge =
+// tiles_merge_kernel's ordered sum and division + post_u8_kernel's clamp and rounding.  Same operations on the same values in the
+// same order, so both equal the two-launch compositions bit for bit.  A thread owns one pixel and its three channels.
+__global__ __launch_bounds__(256) void tiles_gather_u8_kernel(const unsigned char* __restrict__ img, float* __restrict__ tiles,
+                                                              const int* __restrict__ ij, int h, int w, int ch, int cw, int swap_rb) {
+    const long px = (long)blockIdx.x * 256 + threadIdx.x, plane = (long)ch * cw;
+    const int t = blockIdx.z;
+    if (px >= plane) return;
+    const int y = (int)(px / cw), xx = (int)(px - (long)y * cw);
+    const int i = ij[2 * t], j = ij[2 * t + 1];
+    if (i < 0 || j < 0 || i > h - ch || j > w - cw) return;        // an origin outside the frame: nothing is read
+    const unsigned char* p = img + ((long)(i + y) * w + j + xx) * 3;
+    const float c0 = (float)p[0] / 255.0f, c1 = (float)p[1] / 255.0f, c2 = (float)p[2] / 255.0f;   // true division, as pre_u8_kernel
+    float* o = tiles + (long)t * 3 * plane + px;
+    o[0] = swap_rb ? c2 : c0;
+    o[plane] = c1;
+    o[2 * plane] = swap_rb ? c0 : c2;
+}
+
+__global__ __launch_bounds__(256) void tiles_merge_u8_kernel(const float* __restrict__ tiles, unsigned char* __restrict__ out,
+                                                             const int* __restrict__ ij, int T, int h, int w, int ch, int cw, int swap_rb) {
+    const long px = (long)blockIdx.x * 256 + threadIdx.x;
+    if (px >= (long)h * w) return;
+    const int y = (int)(px / w), xx = (int)(px - (long)y * w);
+    const long plane = (long)ch * cw;
+    float acc[3] = {0.f, 0.f, 0.f}, cnt = 0.f;
+    for (int t = 0; t < T; ++t) {
+        const int dy = y - ij[2 * t], dx = xx - ij[2 * t + 1];
+        if (dy >= 0 && dy < ch && dx >= 0 && dx < cw) {
+            const float* s = tiles + (long)t * 3 * plane + (long)dy * cw + dx;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c] += s[c * plane];
+            cnt += 1.0f;
+        }
+    }
+    unsigned char v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float f = acc[c] / cnt;
+        f = f < 0.f ? 0.f : (f > 1.f ? 1.f : f);                    // clamp_(0, 1)
+        v[c] = (unsigned char)rintf(f * 255.0f);                    // numpy .round(): half to even
+    }
+    unsigned char* o = out + px * 3;
+    o[0] = swap_rb ? v[2] : v[0];
+    o[1] = v[1];
+    o[2] = swap_rb ? v[0] : v[2];
+}
+
 }  // namespace
 
 extern "C" int fdn_tiles_gather(const float* x, float* tiles, const int* ij, int T, int C, int H, int W, int ch, int cw,
@@ -86,6 +136,22 @@ extern "C" int fdn_tiles_merge(const float* tiles, float* out, const int* ij, in
     FDN_CHECK_ARG(tiles && out && ij && T > 0 && C > 0 && H > 0 && W > 0 && ch > 0 && cw > 0 && ch <= H && cw <= W && C < 65536);
     hipLaunchKernelGGL(tiles_merge_kernel, dim3(cdiv((long)H * W, 256), C), dim3(256), 0, static_cast<hipStream_t>(stream), tiles, out,
                        ij, T, C, H, W, ch, cw);
+    return fdn_launch_status();
+}
+
+extern "C" int fdn_tiles_gather_u8(const unsigned char* img, float* tiles, const int* ij, int T, int h, int w, int ch, int cw,
+                                   int swap_rb, fdn_stream_t stream) {
+    FDN_CHECK_ARG(img && tiles && ij && T > 0 && h > 0 && w > 0 && ch > 0 && cw > 0 && ch <= h && cw <= w && T < 65536);
+    hipLaunchKernelGGL(tiles_gather_u8_kernel, dim3(cdiv((long)ch * cw, 256), 1, T), dim3(256), 0, static_cast<hipStream_t>(stream), img,
+                       tiles, ij, h, w, ch, cw, swap_rb);
+    return fdn_launch_status();
+}
+
+extern "C" int fdn_tiles_merge_u8(const float* tiles, unsigned char* out, const int* ij, int T, int h, int w, int ch, int cw,
+                                  int swap_rb, fdn_stream_t stream) {
+    FDN_CHECK_ARG(tiles && out && ij && T > 0 && h > 0 && w > 0 && ch > 0 && cw > 0 && ch <= h && cw <= w && T < 65536);
+    hipLaunchKernelGGL(tiles_merge_u8_kernel, dim3(cdiv((long)h * w, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), tiles, out,
+                       ij, T, h, w, ch, cw, swap_rb);
     return fdn_launch_status();
 }
 

@@ -14,6 +14,10 @@ through one forward.  No CPU fallback: the uint8 tensors must live on the ROCm d
 validate_u8 is the same walk with a ground truth beside the input, as the reference's validation does it
 (basicsr/models/image_restoration_model.py:578-586, :650-658, :746-748, :844-848): the ratio from the ground truth (gt_ratio), and
 PSNR / SSIM of the uint8 result against the uint8 ground truth.
+
+With `tile`, a frame larger than one forward can take goes uint8 -> tiling.split_u8 -> tiling.run_tiles -> tiling.merge_u8 -> uint8 (the
+reference's val.grids, image_restoration_model.py:261-339, :737-743), one frame at a time; no fp32 frame exists except the one a
+frame-level ratio is taken from.
 """
 import ctypes
 import torch
@@ -87,14 +91,91 @@ def gt_ratio(x_lq, x_gt):
     return _gray_mean(x_lq) / high
 
 
+def _frame_f32(img_u8, bgr):
+    """uint8 [h,w,3] -> fp32 [1,3,h,w] RGB in [0,1], unpadded: fdn_tiles_gather_u8 with one tile the size of the frame"""
+    h, w, _ = img_u8.shape
+    ij = torch.zeros((1, 2), dtype=torch.int32, device=img_u8.device)
+    out = torch.empty((1, 3, h, w), device=img_u8.device, dtype=torch.float32)
+    check(lib().fdn_tiles_gather_u8(_u8(img_u8, "img"), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ij.data_ptr()), 1, h, w, h, w,
+                                    int(bool(bgr)), stream()), "fdn_tiles_gather_u8")
+    return out
+
+
+def resolve_tile(tile, h, w):
+    """The `tile` keyword for an h x w frame -> None (the untiled path) or (crop_h, crop_w): "auto" is tiling.auto_tile."""
+    from . import tiling
+    if tile is None:
+        return None
+    if isinstance(tile, str):
+        if tile != "auto":
+            raise ValueError(f"tile {tile!r}: None, 'auto' or (crop_h, crop_w)")
+        return tiling.auto_tile(h, w)
+    crop_h, crop_w = tile
+    return int(crop_h), int(crop_w)
+
+
+def _per_tile(fn, tiles, batch):
+    """fn on sub-batches of `batch` tiles, as the forward takes them -> [T,1]"""
+    return torch.cat([fn(tiles[s:s + batch]) for s in range(0, tiles.shape[0], batch)])
+
+
+def tile_ratio(lpnet, img_u8, tiles, ratio_mode, ratio_from, bgr=True, ratio=None, gt_u8=None, batch=8):
+    """The ratio [T,1] that FDN takes on the tiles of one uint8 frame [h,w,3].
+    ratio_from "frame": what the untiled call feeds - LPNet / mean(gray) / gt_ratio on the reflect-padded whole frame (LPNet's tensors are
+    narrow, 16 planes at half resolution, so the whole frame fits) - for every tile alike.
+    ratio_from "tile": the reference's val.grids semantics, where grids() has replaced the frame by its tiles before the ratio is taken
+    (image_restoration_model.py:578-586, :650-654): LPNet / mean(gray) per tile; "gt" is mean(gray(tile)) / mean(gray(ground truth)) with
+    the ground truth whole and unpadded (tiles are multiples of 32, so :583-586 pad nothing).
+    "fixed": the caller's `ratio`, [1,1] for the frame or [T,1]."""
+    if ratio_from not in ("frame", "tile"):
+        raise ValueError(f"ratio_from {ratio_from!r}")
+    T = tiles.shape[0]
+    if ratio_mode == "fixed":
+        if ratio is None or ratio.dim() != 2 or ratio.shape[1] != 1 or ratio.shape[0] not in (1, T):
+            raise FdnHipError(f"ratio_mode 'fixed' on {T} tiles needs ratio [1,1] or [{T},1]")
+        return ratio.to(device=tiles.device, dtype=torch.float32).expand(T, 1).contiguous()
+    if ratio_mode == "gt" and gt_u8 is None:
+        raise FdnHipError("ratio_mode 'gt' needs the ground-truth frame")
+    if ratio_mode != "gt" and lpnet is None:
+        raise FdnHipError(f"ratio_mode {ratio_mode!r} needs lpnet")
+    if ratio_from == "frame":
+        x = preprocess(img_u8, bgr=bgr)[0]
+        if ratio_mode == "gt":
+            r = gt_ratio(x, preprocess(gt_u8, bgr=bgr)[0])
+        elif ratio_mode == "lolblur":
+            r = lpnet(x)
+        else:
+            r = lolv1_ratio(x, lpnet(x))
+        return r.expand(T, 1).contiguous()
+    if ratio_mode == "lolblur":
+        return _per_tile(lpnet, tiles, batch)
+    if ratio_mode == "lolv1":
+        return _per_tile(lambda t: lolv1_ratio(t, lpnet(t)), tiles, batch)
+    high = _gray_mean(_frame_f32(gt_u8, bgr))
+    if bool((high == 0).any()):
+        raise FdnHipError("gt_ratio: a ground-truth image has gray mean 0")
+    return _per_tile(_gray_mean, tiles, batch) / high
+
+
 @torch.no_grad()
-def enhance_u8(net, lpnet, img_u8, bgr=True, ratio_mode="lolblur", ratio=None):
+def enhance_u8(net, lpnet, img_u8, bgr=True, ratio_mode="lolblur", ratio=None, tile=None, ratio_from="frame", overlap=0, batch=8):
     """uint8 in -> uint8 out through LPNet -> FDN (the body of the reference's per-image loop, batched).
     ratio_mode: "lolblur" feeds LPNet's prediction (inference_fdn_lolblur.py:69-71), "lolv1" feeds
     mean(gray)/prediction (inference_fdn_lolv1.py:57-62), "fixed" feeds the caller's `ratio` [B,1] and skips LPNet - the
-    ratio sweep of inference_fdn_multi_r.py:78-84 (`ratio = ratio / ratio * i`)."""
+    ratio sweep of inference_fdn_multi_r.py:78-84 (`ratio = ratio / ratio * i`).
+    tile: None = every frame in one forward; (crop_h, crop_w), multiples of 32, or "auto" (tiling.auto_tile: only frames above
+    tiling.WHOLE_FRAME_MAX_PIXELS) = frame by frame through enhance_frame_tiled, `batch` tiles per forward, neighbours sharing at least
+    `overlap` pixels, the ratio taken from the whole frame or per tile (ratio_from, see tile_ratio; "fixed" then also takes [B,T,1])."""
     if ratio_mode not in ("lolblur", "lolv1", "fixed"):
         raise ValueError(f"ratio_mode {ratio_mode!r}")
+    if img_u8.dim() == 3:
+        img_u8 = img_u8.unsqueeze(0)
+    if tile is not None and img_u8.dim() == 4 and resolve_tile(tile, img_u8.shape[1], img_u8.shape[2]) is not None:
+        if ratio_mode == "fixed" and (ratio is None or ratio.shape[0] != img_u8.shape[0]):
+            raise FdnHipError(f"ratio_mode 'fixed' needs ratio [B,1] or [B,T,1] for B = {img_u8.shape[0]}")
+        return torch.stack([enhance_frame_tiled(net, lpnet, img_u8[b], tile, bgr=bgr, ratio_mode=ratio_mode, ratio_from=ratio_from,
+                                                ratio=None if ratio is None else ratio[b].reshape(-1, 1), overlap=overlap, batch=batch)[0]
+                            for b in range(img_u8.shape[0])])
     x, h, w = preprocess(img_u8, bgr=bgr)
     if ratio_mode == "fixed":
         if ratio is None or tuple(ratio.shape) != (x.shape[0], 1):
@@ -110,13 +191,34 @@ def enhance_u8(net, lpnet, img_u8, bgr=True, ratio_mode="lolblur", ratio=None):
 
 
 @torch.no_grad()
-def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=True):
+def enhance_frame_tiled(net, lpnet, img_u8, tile, bgr=True, ratio_mode="lolblur", ratio_from="frame", ratio=None, gt_u8=None, overlap=0,
+                        batch=8, run=None):
+    """One uint8 frame [h,w,3] through the tiled route -> (uint8 [h,w,3], ratio [T,1]).  tile: (crop_h, crop_w) or "auto" (which must
+    resolve to a tile here); ratio_mode / ratio_from / ratio / gt_u8 as tile_ratio takes them.  run(tiles, ratio) -> outs replaces
+    tiling.run_tiles(net, tiles, ratio, batch) - the drivers pass the root's side of tiling.run_tiles_sharded."""
+    from . import tiling
+    if img_u8.dim() != 3 or img_u8.shape[-1] != 3:
+        raise FdnHipError(f"expected one uint8 frame [h,w,3], got {tuple(img_u8.shape)}")
+    h, w, _ = img_u8.shape
+    crop = resolve_tile(tile, h, w)
+    if crop is None:
+        raise FdnHipError(f"a {h}x{w} frame needs no tile: run it on the untiled path")
+    tiles, ij = tiling.split_u8(img_u8, crop[0], crop[1], bgr=bgr, overlap=overlap)
+    r = tile_ratio(lpnet, img_u8, tiles, ratio_mode, ratio_from, bgr=bgr, ratio=ratio, gt_u8=gt_u8, batch=batch)
+    outs = tiling.run_tiles(net, tiles, r, batch) if run is None else run(tiles, r)
+    return tiling.merge_u8(outs, ij, h, w, bgr=bgr), r
+
+
+@torch.no_grad()
+def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=True, tile=None, ratio_from="frame", overlap=0, batch=8):
     """One validation step of the reference (image_restoration_model.py:578-586, :650-658, :746-748, :844-848) for a batch, on the device:
     uint8 low-quality and ground-truth frames [B,h,w,3] -> (uint8 result [B,h,w,3], PSNR list, SSIM list, ratio [B,1]).
     ratio_mode: "gt" feeds mean(gray(lq)) / mean(gray(gt)) as the validation does (gt_ratio; lpnet is not used and may be None),
     "lolblur" / "lolv1" feed LPNet's ratio as enhance_u8 does.  The scores are calculate_psnr / calculate_ssim of the uint8 result
     (img1) against gt_u8, as the reference scores tensor2img's images (fdn_hip.metrics.calculate_psnr_ssim_u8).  Eager forward on the
-    caller's stream."""
+    caller's stream.
+    tile / ratio_from / overlap / batch as in enhance_u8; ratio_from "tile" is the reference's val.grids validation.  With a tile the
+    returned ratio is [B,T,1], one row per tile."""
     from .metrics import calculate_psnr_ssim_u8
     if ratio_mode not in ("gt", "lolblur", "lolv1"):
         raise ValueError(f"ratio_mode {ratio_mode!r}")
@@ -128,6 +230,12 @@ def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=Tr
         gt_u8 = gt_u8.unsqueeze(0)
     if lq_u8.shape != gt_u8.shape:
         raise FdnHipError(f"Image shapes are different: {tuple(lq_u8.shape)}, {tuple(gt_u8.shape)}.")
+    if tile is not None and lq_u8.dim() == 4 and resolve_tile(tile, lq_u8.shape[1], lq_u8.shape[2]) is not None:
+        done = [enhance_frame_tiled(net, lpnet, lq_u8[b], tile, bgr=bgr, ratio_mode=ratio_mode, ratio_from=ratio_from, gt_u8=gt_u8[b],
+                                    overlap=overlap, batch=batch) for b in range(lq_u8.shape[0])]
+        out = torch.stack([o for o, _ in done])
+        psnr, ssim = calculate_psnr_ssim_u8(out, gt_u8, crop_border=crop_border, bgr=bgr)
+        return out, psnr, ssim, torch.stack([r for _, r in done])
     x, h, w = preprocess(lq_u8, bgr=bgr)
     if ratio_mode == "gt":
         ratio = gt_ratio(x, preprocess(gt_u8, bgr=bgr)[0])

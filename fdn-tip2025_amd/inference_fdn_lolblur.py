@@ -8,6 +8,11 @@ Images of equal size are batched (the reference runs batch 1; every op of the pa
 Needs a ROCm GPU and the built libfdn_hip.so; there is no CPU fallback.
 
     python inference_fdn_lolblur.py --fdn FDN_lolblur.pth --lpnet LPNet_lolblur.pth --input 'frames/*.png' --output out/
+
+A frame larger than one forward can take (a 12 MP photo) runs with --tile HxW or --tile auto: overlapping tiles as the reference's
+val.grids cuts them, each through FDN, averaged where they overlap; the ratio comes from the whole frame (--tile-ratio frame) or from
+each tile (tile: the reference's semantics).  Under `python -m torch.distributed.run --nproc_per_node N` with --tile, rank 0 reads,
+splits, merges and writes, and the tiles of each frame are dealt to all N GPUs.
 """
 import argparse
 import glob
@@ -38,6 +43,47 @@ def load_params(path):
     return sd["params"] if isinstance(sd, dict) and "params" in sd else sd     # inference_fdn_lolblur.py:28,31
 
 
+def tile_arg(s):
+    """--tile: 'off' -> None, 'auto' -> "auto", 'HxW' with both numbers positive multiples of 32 -> (H, W)"""
+    if s in ("off", "auto"):
+        return None if s == "off" else s
+    try:
+        h, w = (int(v) for v in s.lower().split("x"))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{s!r} is not HxW, auto or off")
+    if h <= 0 or w <= 0 or h % 32 or w % 32:
+        raise argparse.ArgumentTypeError(f"{s!r}: both tile sizes must be positive multiples of 32")
+    return h, w
+
+
+def add_tile_args(ap, ratio_default="frame"):
+    """--tile / --tile-overlap, and --tile-ratio unless ratio_default is None (a driver whose ratio is fixed)"""
+    ap.add_argument("--tile", type=tile_arg, default=None, metavar="HxW|auto|off",
+                    help="run frames as overlapping tiles of this size (multiples of 32), merged by averaging; auto: 736x1280 tiles for "
+                         "frames above 1088x1920 pixels only; default off")
+    ap.add_argument("--tile-overlap", type=int, default=0, metavar="N",
+                    help="least number of pixels neighbouring tiles share (default 0: the reference's rule, no overlap when a side is a "
+                         "multiple of the tile)")
+    if ratio_default is not None:
+        ap.add_argument("--tile-ratio", choices=("frame", "tile"), default=ratio_default,
+                        help=f"take the ratio from the whole frame or from each tile (default {ratio_default})")
+
+
+_hinted = False
+
+
+def hint_large_frame(tile, h, w):
+    """one line on stderr, once per run, when an untiled frame is larger than the whole-frame path is tested at"""
+    global _hinted
+    from fdn_hip.harness import padded_size
+    from fdn_hip.tiling import WHOLE_FRAME_MAX_PIXELS
+    H, W = padded_size(h, w)
+    if tile is None and not _hinted and H * W > WHOLE_FRAME_MAX_PIXELS:
+        _hinted = True
+        print(f"note: a {h}x{w} frame is larger than a whole-frame forward is tested at (1088x1920 padded); --tile auto runs it in tiles",
+              file=sys.stderr)
+
+
 def run_driver(doc, build_models, ratio_mode="lolblur", fdn_keys="FDN checkpoint ({'params': state_dict}, 1503 keys)"):
     """The directory walk shared by the LOL-Blur and LOL-v1 drivers: build_models() -> (FDN-like module, LPNet module) on the CPU,
     ratio_mode as fdn_hip.harness.enhance_u8 takes it."""
@@ -52,18 +98,60 @@ def run_driver(doc, build_models, ratio_mode="lolblur", fdn_keys="FDN checkpoint
                          "default: the common parent directory of all input frames")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--device", default="cuda:0")
+    add_tile_args(ap)
     a = ap.parse_args()
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world > 1 and a.tile is None:
+        ap.error("WORLD_SIZE > 1 needs --tile: the ranks share the tiles of one frame; sharding whole frames by file is not supported")
 
-    from fdn_hip.harness import enhance_u8
+    from fdn_hip import tiling
+    from fdn_hip.harness import enhance_frame_tiled, enhance_u8, resolve_tile
 
+    dist = None
     dev = torch.device(a.device)
+    if world > 1:
+        import torch.distributed as dist
+        dev = torch.device("cuda", int(os.environ["LOCAL_RANK"]))
     torch.cuda.set_device(dev)
+    if dist is not None:
+        dist.init_process_group("nccl")
     net, lp = build_models()
     net = net.to(dev).eval()
     net.load_state_dict(load_params(a.fdn), strict=True)
     lp = lp.to(dev).eval()
     lp.load_state_dict(load_params(a.lpnet), strict=True)
 
+    tile_kw = dict(ratio_from=a.tile_ratio, overlap=a.tile_overlap, batch=a.batch)
+
+    def serve(tiles, ratio):
+        return tiling.run_tiles(net, tiles, ratio, a.batch)
+
+    if dist is not None and dist.get_rank() != 0:
+        tiling.serve_tiles(dist, serve, dev)                              # until rank 0 has written its last frame
+        dist.destroy_process_group()
+        return
+
+    def enhance(batch):
+        """uint8 [B,h,w,3] -> uint8 [B,h,w,3]; with more than one rank the tiles of each frame go through all of them"""
+        h, w = batch.shape[1:3]
+        hint_large_frame(a.tile, h, w)
+        if dist is None:
+            return enhance_u8(net, lp, batch, bgr=False, ratio_mode=ratio_mode, tile=a.tile, **tile_kw)
+        if resolve_tile(a.tile, h, w) is None:
+            return enhance_u8(net, lp, batch, bgr=False, ratio_mode=ratio_mode)
+        return torch.stack([enhance_frame_tiled(net, lp, img, a.tile, bgr=False, ratio_mode=ratio_mode,
+                                                run=lambda t, r: tiling.run_tiles_root(dist, serve, t, r), **tile_kw)[0] for img in batch])
+
+    try:
+        walk(a, dev, enhance)
+    finally:
+        if dist is not None:
+            tiling.end_serving(dist)
+            dist.destroy_process_group()
+
+
+def walk(a, dev, enhance):
+    """decode -> enhance(uint8 batch on the device) -> encode over the frames of a.input"""
     paths = sorted(glob.glob(a.input))
     if not paths:
         raise SystemExit(f"no input frames match {a.input}")
@@ -81,7 +169,7 @@ def run_driver(doc, build_models, ratio_mode="lolblur", fdn_keys="FDN checkpoint
             if not pending:
                 return
             batch = torch.from_numpy(np.stack([im for _, im in pending])).to(dev, non_blocking=True)
-            out = enhance_u8(net, lp, batch, bgr=False, ratio_mode=ratio_mode).cpu().numpy()
+            out = enhance(batch).cpu().numpy()
             for (p, _), o in zip(pending, out):
                 writers.append(pool.submit(write_rgb, dest[p], o))
             pending.clear()

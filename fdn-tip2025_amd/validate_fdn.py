@@ -10,6 +10,10 @@ and paired by index; frames of equal size are batched and decoded one batch ahea
 scores take one small copy per batch.  Needs a ROCm GPU and the built libfdn_hip.so; there is no CPU fallback.
 
     python validate_fdn.py --fdn FDN_lolblur.pth --lq 'lolblur/test/low_blur/*/*' --gt 'lolblur/test/high_sharp_scaled/*/*' --csv scores.csv
+
+--tile HxW plays the reference's `val.grids` with crop_size_h / crop_size_w (:261-339, :737-743): every frame is cut into overlapping tiles,
+the ratio is taken per tile as the reference does after grids() (--tile-ratio tile, the default here; frame: one ratio from the whole
+frame), and the merged 8-bit frame is scored.  The csv then holds one ratio per tile, joined by ';'.
 """
 import argparse
 import glob
@@ -56,6 +60,8 @@ def parse_args(argv=None):
     ap.add_argument("--csv", default=None, help="file for one 'frame,psnr,ssim,ratio' line per pair")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--device", default="cuda:0")
+    from inference_fdn_lolblur import add_tile_args
+    add_tile_args(ap, ratio_default="tile")
     a = ap.parse_args(argv)
     if a.ratio == "lpnet" and not a.lpnet:
         ap.error("--ratio lpnet needs --lpnet")
@@ -73,7 +79,7 @@ def main(argv=None):
     a = parse_args(argv)
     import torch
     from fdn_hip.harness import validate_u8
-    from inference_fdn_lolblur import load_params, write_rgb
+    from inference_fdn_lolblur import hint_large_frame, load_params, write_rgb
     from basicsr.models.archs.LPNet_arch import I_predict_net
     if a.variant == "lolblur":
         from basicsr.models.archs.FDN_arch import FDN as Net
@@ -96,8 +102,10 @@ def main(argv=None):
         writers = []
         for idx, lqs, gts in decoded_groups(a.pairs, a.batch, pool):
             lq, gt = torch.from_numpy(lqs).to(dev), torch.from_numpy(gts).to(dev)
-            out, p, s, r = validate_u8(net, lp, lq, gt, ratio_mode=mode, crop_border=a.crop_border, bgr=False)
-            r = r.reshape(-1).cpu().tolist()
+            hint_large_frame(a.tile, lqs.shape[1], lqs.shape[2])
+            out, p, s, r = validate_u8(net, lp, lq, gt, ratio_mode=mode, crop_border=a.crop_border, bgr=False, tile=a.tile,
+                                       ratio_from=a.tile_ratio, overlap=a.tile_overlap, batch=a.batch)
+            r = r.reshape(r.shape[0], -1).cpu().tolist()              # one ratio per frame, or one per tile of a tiled frame
             frames = out.cpu().numpy() if a.dest else None
             for k, i in enumerate(idx):
                 psnr[i], ssim[i], ratio[i] = p[k], s[k], r[k]
@@ -114,7 +122,7 @@ def main(argv=None):
         with open(a.csv, "w") as f:
             f.write("frame,psnr,ssim,ratio\n")
             for (lq_path, _), p, s, r in zip(a.pairs, psnr, ssim, ratio):
-                f.write(f"{lq_path},{p!r},{s!r},{r!r}\n")
+                f.write(f"{lq_path},{p!r},{s!r},{';'.join(repr(v) for v in r)}\n")
     if a.dest:
         print(f"{n} frames -> {a.output}")
 

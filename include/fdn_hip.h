@@ -36,7 +36,7 @@ enum { FDN_PRO_NONE = 0, FDN_PRO_LN = 1, FDN_PRO_LN3_GATE = 2, FDN_PRO_LN_MULADD
 enum { FDN_EPI_NONE = 0, FDN_EPI_RES = 1, FDN_EPI_MULADD = 2 };
 enum { FDN_RS_BILINEAR_HALF = 0, FDN_RS_BILINEAR_X2 = 1, FDN_RS_NEAREST_HALF = 2, FDN_RS_NEAREST_X2 = 3, FDN_RS_PIXEL_UNSHUFFLE = 4 };
 
-/* library version / build info: returns the ABI version (bumped on any signature change; 20 since the fdn_pair_* entry points) */
+/* library version / build info: returns the ABI version (bumped on any signature change; 21 since fdn_tiles_gather_u8 / fdn_tiles_merge_u8) */
 int fdn_abi_version(void);
 const char* fdn_error_string(int code);
 /* Diagnostic switch, process-wide, default 0 = every matrix product that has a split-bf16 form runs on the bf16 matrix pipe
@@ -369,6 +369,18 @@ int fdn_post_u8(const float* res, unsigned char* out, int B, int h, int w, int H
  * fdn_tiles_merge : tiles [T][C][ch][cw] -> out [C][H][W] = (sum of the tiles covering a pixel, in tile order) / count. */
 int fdn_tiles_gather(const float* x, float* tiles, const int* ij, int T, int C, int H, int W, int ch, int cw, fdn_stream_t stream);
 int fdn_tiles_merge(const float* tiles, float* out, const int* ij, int T, int C, int H, int W, int ch, int cw, fdn_stream_t stream);
+/* ABI 21.  The same pair between a uint8 frame and fp32 tiles, so that a frame larger than one forward can take never exists in fp32
+ * (no reference counterpart: grids() runs after the host has converted the frame).  Same ij; T < 65536, ch <= h, cw <= w.
+ * fdn_tiles_gather_u8: img [h][w][3] uint8 -> tiles [T][3][ch][cw], tiles[t][c][y][x] = (float)img[i_t + y][j_t + x][c'] / 255.0f with
+ *   c' = 2 - c when swap_rb (BGR input) else c: bit for bit fdn_pre_u8(H = h, W = w) then fdn_tiles_gather(C = 3).  No reflect padding:
+ *   the tiles are cut from the frame itself.  A tile whose origin lies outside [0, h - ch] x [0, w - cw] is left unwritten.
+ * fdn_tiles_merge_u8: tiles [T][3][ch][cw] -> out [h][w][3] uint8 = rintf(clamp(acc / cnt, 0, 1) * 255), acc the fp32 sum in tile order
+ *   of the tiles covering the pixel and cnt their number: bit for bit fdn_tiles_merge then fdn_post_u8(H = h, W = w) for finite
+ *   inputs; swap_rb = 1 writes BGR.  Every pixel must be covered by a tile (origins of the grids() walk always do). */
+int fdn_tiles_gather_u8(const unsigned char* img, float* tiles, const int* ij, int T, int h, int w, int ch, int cw, int swap_rb,
+                        fdn_stream_t stream);
+int fdn_tiles_merge_u8(const float* tiles, unsigned char* out, const int* ij, int T, int h, int w, int ch, int cw, int swap_rb,
+                       fdn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Validation metrics on the GPU (basicsr/metrics/psnr_ssim.py:8-73, :163-197).
