@@ -290,6 +290,19 @@ __global__ __launch_bounds__(256) void convT_quad_kernel(const float* __restrict
     }
 }
 
+// One axis of the bilinear x2 blend (1 - l) p + l q.  align_corners=False puts l in {0, 0.25, 0.75}: the product by 0.25 (or by 0) is exact, so as
+// the addend of the FMA that forms the other product it leaves the blend with ONE rounding.  Spelled with fmaf and contraction off: left to the
+// compiler, which product gets fused is chosen per kernel (and per row of a vectorised pair), and resample_kernel and resample4_kernel came out an
+// ulp apart although they state the same expression.
+__device__ __forceinline__ float blend_x2(float l, float p, float q) {
+#pragma clang fp contract(off)
+    const float m = 1.f - l;
+    return l < 0.5f ? fmaf(m, p, l * q) : fmaf(l, q, m * p);
+}
+__device__ __forceinline__ float bilinear_x2(float ly, float lx, float p, float q, float u, float v) {      // rows (p, q) and (u, v)
+    return blend_x2(ly, blend_x2(lx, p, q), blend_x2(lx, u, v));
+}
+
 __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__ x, float* __restrict__ out, long planes, int H,
                                                        int W, int OH, int OW, int mode, int r) {
     // grid = (column blocks, output rows, output planes): no per-element division (the flat index form spent ~100 instructions
@@ -309,8 +322,7 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
         const int y1 = min(y0 + 1, H - 1), x1 = min(x0 + 1, W - 1);
         const float ly = sy - y0, lx = sx - x0;
         const float* s = x + pl * H * W;
-        out[idx] = (1.f - ly) * ((1.f - lx) * s[(long)y0 * W + x0] + lx * s[(long)y0 * W + x1]) +
-                   ly * ((1.f - lx) * s[(long)y1 * W + x0] + lx * s[(long)y1 * W + x1]);
+        out[idx] = bilinear_x2(ly, lx, s[(long)y0 * W + x0], s[(long)y0 * W + x1], s[(long)y1 * W + x0], s[(long)y1 * W + x1]);
     } else if (mode == FDN_RS_NEAREST_HALF) {
         out[idx] = x[pl * H * W + (long)(2 * oy) * W + 2 * ox];
     } else if (mode == FDN_RS_NEAREST_X2) {
@@ -324,7 +336,7 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
 }
 
 // Four outputs per thread for the bilinear modes and nearest x2 (16-byte stores, the source window loaded once): the same arithmetic
-// per value as resample_kernel, so the results are bit-identical to it.  grid = ((output rows x column quads) / 256, planes).
+// per value as resample_kernel (bilinear_x2 above; the 1/2 mode multiplies by 0.5 only, which is exact), so the results are bit-identical to it.  grid = ((output rows x column quads) / 256, planes).
 template <int MODE>
 __global__ __launch_bounds__(256) void resample4_kernel(const float* __restrict__ x, float* __restrict__ out, int H, int W, int OH,
                                                         int OW) {
@@ -359,7 +371,7 @@ __global__ __launch_bounds__(256) void resample4_kernel(const float* __restrict_
         const int cm = max(2 * t - 1, 0), c0 = 2 * t, c1 = min(2 * t + 1, W - 1), c2 = min(2 * t + 2, W - 1);
         const float am = r0[cm], a0 = r0[c0], a1 = r0[c1], a2 = r0[c2];
         const float bm = r1[cm], b0 = r1[c0], b1 = r1[c1], b2 = r1[c2];
-        auto mix = [&](float lx, float p, float q, float u, float v) { return (1.f - ly) * ((1.f - lx) * p + lx * q) + ly * ((1.f - lx) * u + lx * v); };
+        auto mix = [&](float lx, float p, float q, float u, float v) { return bilinear_x2(ly, lx, p, q, u, v); };
         o.x = t == 0 ? mix(0.f, a0, a1, b0, b1) : mix(0.75f, am, a0, bm, b0);      // (output 0 of a row: source x clamps to 0)
         o.y = mix(0.25f, a0, a1, b0, b1);
         o.z = mix(0.75f, a0, a1, b0, b1);

@@ -368,13 +368,21 @@ def _seblock(x, P, pfx, stride, proj):
     return F.relu(y + sc)
 
 
-def lpnet_forward(P, x):
-    """I_predict_net.forward(x, use_ori_i=False), LPNet_arch.py:114-134 -> (B,1)."""
+def lpnet_forward(P, x, taps=None):
+    """I_predict_net.forward(x, use_ori_i=False), LPNet_arch.py:114-134 -> (B,1).  taps: optional dict that receives the stem
+    output (conv + BN + ReLU) as 'stem', the pooled map as 'pool' and the outputs of the three stages as 'conv2', 'conv3', 'conv4'
+    (what forward hooks on those modules see)."""
     y = F.relu(_bn(F.conv2d(x, P["conv1.0.weight"], stride=2, padding=3), P, "conv1.1"))
+    if taps is not None:
+        taps.update(stem=y)
     y = F.avg_pool2d(y, 3, 2, 1)   # count_include_pad=True (nn.AvgPool2d default), LPNet_arch.py:94
+    if taps is not None:
+        taps.update(pool=y)
     for name, num, stride in (("conv2", 3, 1), ("conv3", 3, 2), ("conv4", 6, 6)):
         for i in range(num):
             y = _seblock(y, P, f"{name}.{i}", stride if i == 0 else 1, i == 0)
+        if taps is not None:
+            taps[name] = y
     y = y.mean(dim=(2, 3))          # GAP then "B C H W -> B (H W C)" with H=W=1
     y = F.linear(y, P["fc.0.weight"], P["fc.0.bias"])
     y = F.linear(y, P["fc2.0.weight"], P["fc2.0.bias"])

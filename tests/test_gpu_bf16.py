@@ -97,6 +97,24 @@ def test_bf16_is_storage_only(A, C, H, W):
     assert t16 is not None and torch.equal(t16, t32) and torch.equal(t16._fdn_stats, t32._fdn_stats)
 
 
+@pytest.mark.parametrize("C,H,W", [(32, 8, 6), (24, 4, 70)])
+def test_bf16_gate_dword_forms(A, C, H, W):
+    """The gate step of the chain above alone (its FFT kernels need whole 8 x 8 patches) where H * W % 4 == 0 but W % 4 != 0, e.g. a
+    100 x 150 level: bf16 storage is on and fdn_dwconv_gate runs its <false, IBF, OBF> forms (2-byte loads and stores at odd element
+    offsets); 70 columns need a second 64-column tile."""
+    from fdn_hip import ops
+    Hd, B = int(C * 2.7), 2
+    assert H * W % 4 == 0 and W % 4 != 0
+    y16 = dev(_rnd(B, Hd, H, W, seed=1)).to(BF)
+    wg = dev(_rnd(2 * Hd, 1, 3, 3, seed=9) / 3)
+    g32 = ops.dwconv_gate(y16.float(), wg)
+    assert torch.equal(ops.dwconv_gate(y16, wg, out_dtype=torch.float32), g32)
+    g16 = ops.dwconv_gate(y16, wg)
+    assert g16.dtype == BF and torch.equal(g16, g32.to(BF))
+    x1, x2 = torch.nn.functional.conv2d(y16.double().cpu(), wg.double().cpu(), padding=1, groups=Hd).chunk(2, dim=1)
+    assert rel_rms(g32.cpu(), torch.nn.functional.gelu(x1) * x2) < 2e-6
+
+
 @pytest.mark.parametrize("name,cls,c", [("fdsa_c32", "FDSA", 32), ("fdsa_c64", "FDSA", 64), ("fdffn_c32", "FDFFN", 32), ("fdffn_c64", "FDFFN", 64)])
 def test_bf16_block_accuracy(A, name, cls, c):
     """One block in bf16-storage mode against the fp32 reference fixture."""
