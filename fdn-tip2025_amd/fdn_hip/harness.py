@@ -17,7 +17,7 @@ PSNR / SSIM of the uint8 result against the uint8 ground truth.
 
 With `tile`, a frame larger than one forward can take goes uint8 -> tiling.split_u8 -> tiling.run_tiles -> tiling.merge_u8 -> uint8 (the
 reference's val.grids, image_restoration_model.py:261-339, :737-743), one frame at a time; no fp32 frame exists except the one a
-frame-level ratio is taken from.
+frame-level ratio is taken from.  blend="feather" merges the tiles with ramps across their overlaps instead of the reference's average.
 """
 import ctypes
 import torch
@@ -158,23 +158,28 @@ def tile_ratio(lpnet, img_u8, tiles, ratio_mode, ratio_from, bgr=True, ratio=Non
 
 
 @torch.no_grad()
-def enhance_u8(net, lpnet, img_u8, bgr=True, ratio_mode="lolblur", ratio=None, tile=None, ratio_from="frame", overlap=0, batch=8):
+def enhance_u8(net, lpnet, img_u8, bgr=True, ratio_mode="lolblur", ratio=None, tile=None, ratio_from="frame", overlap=0, batch=8,
+               blend="average"):
     """uint8 in -> uint8 out through LPNet -> FDN (the body of the reference's per-image loop, batched).
     ratio_mode: "lolblur" feeds LPNet's prediction (inference_fdn_lolblur.py:69-71), "lolv1" feeds
     mean(gray)/prediction (inference_fdn_lolv1.py:57-62), "fixed" feeds the caller's `ratio` [B,1] and skips LPNet - the
     ratio sweep of inference_fdn_multi_r.py:78-84 (`ratio = ratio / ratio * i`).
     tile: None = every frame in one forward; (crop_h, crop_w), multiples of 32, or "auto" (tiling.auto_tile: only frames above
     tiling.WHOLE_FRAME_MAX_PIXELS) = frame by frame through enhance_frame_tiled, `batch` tiles per forward, neighbours sharing at least
-    `overlap` pixels, the ratio taken from the whole frame or per tile (ratio_from, see tile_ratio; "fixed" then also takes [B,T,1])."""
+    `overlap` pixels, the ratio taken from the whole frame or per tile (ratio_from, see tile_ratio; "fixed" then also takes [B,T,1]),
+    the tiles merged by the reference's average or feathered (blend, see tiling.merge).  Without a tile, blend does nothing."""
+    from .tiling import check_blend
     if ratio_mode not in ("lolblur", "lolv1", "fixed"):
         raise ValueError(f"ratio_mode {ratio_mode!r}")
+    check_blend(blend)
     if img_u8.dim() == 3:
         img_u8 = img_u8.unsqueeze(0)
     if tile is not None and img_u8.dim() == 4 and resolve_tile(tile, img_u8.shape[1], img_u8.shape[2]) is not None:
         if ratio_mode == "fixed" and (ratio is None or ratio.shape[0] != img_u8.shape[0]):
             raise FdnHipError(f"ratio_mode 'fixed' needs ratio [B,1] or [B,T,1] for B = {img_u8.shape[0]}")
         return torch.stack([enhance_frame_tiled(net, lpnet, img_u8[b], tile, bgr=bgr, ratio_mode=ratio_mode, ratio_from=ratio_from,
-                                                ratio=None if ratio is None else ratio[b].reshape(-1, 1), overlap=overlap, batch=batch)[0]
+                                                ratio=None if ratio is None else ratio[b].reshape(-1, 1), overlap=overlap, batch=batch,
+                                                blend=blend)[0]
                             for b in range(img_u8.shape[0])])
     x, h, w = preprocess(img_u8, bgr=bgr)
     if ratio_mode == "fixed":
@@ -192,11 +197,13 @@ def enhance_u8(net, lpnet, img_u8, bgr=True, ratio_mode="lolblur", ratio=None, t
 
 @torch.no_grad()
 def enhance_frame_tiled(net, lpnet, img_u8, tile, bgr=True, ratio_mode="lolblur", ratio_from="frame", ratio=None, gt_u8=None, overlap=0,
-                        batch=8, run=None):
+                        batch=8, run=None, blend="average"):
     """One uint8 frame [h,w,3] through the tiled route -> (uint8 [h,w,3], ratio [T,1]).  tile: (crop_h, crop_w) or "auto" (which must
     resolve to a tile here); ratio_mode / ratio_from / ratio / gt_u8 as tile_ratio takes them.  run(tiles, ratio) -> outs replaces
-    tiling.run_tiles(net, tiles, ratio, batch) - the drivers pass the root's side of tiling.run_tiles_sharded."""
+    tiling.run_tiles(net, tiles, ratio, batch) - the drivers pass the root's side of tiling.run_tiles_sharded.  blend: how the tiles are
+    merged, "average" or "feather" (tiling.merge_u8); the merge runs here, on the root, whoever ran the tiles."""
     from . import tiling
+    tiling.check_blend(blend)
     if img_u8.dim() != 3 or img_u8.shape[-1] != 3:
         raise FdnHipError(f"expected one uint8 frame [h,w,3], got {tuple(img_u8.shape)}")
     h, w, _ = img_u8.shape
@@ -206,22 +213,25 @@ def enhance_frame_tiled(net, lpnet, img_u8, tile, bgr=True, ratio_mode="lolblur"
     tiles, ij = tiling.split_u8(img_u8, crop[0], crop[1], bgr=bgr, overlap=overlap)
     r = tile_ratio(lpnet, img_u8, tiles, ratio_mode, ratio_from, bgr=bgr, ratio=ratio, gt_u8=gt_u8, batch=batch)
     outs = tiling.run_tiles(net, tiles, r, batch) if run is None else run(tiles, r)
-    return tiling.merge_u8(outs, ij, h, w, bgr=bgr), r
+    return tiling.merge_u8(outs, ij, h, w, bgr=bgr, blend=blend), r
 
 
 @torch.no_grad()
-def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=True, tile=None, ratio_from="frame", overlap=0, batch=8):
+def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=True, tile=None, ratio_from="frame", overlap=0, batch=8,
+                blend="average"):
     """One validation step of the reference (image_restoration_model.py:578-586, :650-658, :746-748, :844-848) for a batch, on the device:
     uint8 low-quality and ground-truth frames [B,h,w,3] -> (uint8 result [B,h,w,3], PSNR list, SSIM list, ratio [B,1]).
     ratio_mode: "gt" feeds mean(gray(lq)) / mean(gray(gt)) as the validation does (gt_ratio; lpnet is not used and may be None),
     "lolblur" / "lolv1" feed LPNet's ratio as enhance_u8 does.  The scores are calculate_psnr / calculate_ssim of the uint8 result
     (img1) against gt_u8, as the reference scores tensor2img's images (fdn_hip.metrics.calculate_psnr_ssim_u8).  Eager forward on the
     caller's stream.
-    tile / ratio_from / overlap / batch as in enhance_u8; ratio_from "tile" is the reference's val.grids validation.  With a tile the
-    returned ratio is [B,T,1], one row per tile."""
+    tile / ratio_from / overlap / batch / blend as in enhance_u8; ratio_from "tile" is the reference's val.grids validation.  With a tile
+    the returned ratio is [B,T,1], one row per tile."""
     from .metrics import calculate_psnr_ssim_u8
+    from .tiling import check_blend
     if ratio_mode not in ("gt", "lolblur", "lolv1"):
         raise ValueError(f"ratio_mode {ratio_mode!r}")
+    check_blend(blend)
     if ratio_mode != "gt" and lpnet is None:
         raise FdnHipError(f"ratio_mode {ratio_mode!r} needs lpnet")
     if lq_u8.dim() == 3:
@@ -232,7 +242,7 @@ def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=Tr
         raise FdnHipError(f"Image shapes are different: {tuple(lq_u8.shape)}, {tuple(gt_u8.shape)}.")
     if tile is not None and lq_u8.dim() == 4 and resolve_tile(tile, lq_u8.shape[1], lq_u8.shape[2]) is not None:
         done = [enhance_frame_tiled(net, lpnet, lq_u8[b], tile, bgr=bgr, ratio_mode=ratio_mode, ratio_from=ratio_from, gt_u8=gt_u8[b],
-                                    overlap=overlap, batch=batch) for b in range(lq_u8.shape[0])]
+                                    overlap=overlap, batch=batch, blend=blend) for b in range(lq_u8.shape[0])]
         out = torch.stack([o for o, _ in done])
         psnr, ssim = calculate_psnr_ssim_u8(out, gt_u8, crop_border=crop_border, bgr=bgr)
         return out, psnr, ssim, torch.stack([r for _, r in done])

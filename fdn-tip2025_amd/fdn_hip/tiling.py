@@ -3,10 +3,14 @@
 `val.grids` with `crop_size_h/w`, :737-743).  Tiles overlap by an adaptive step, run through the network as a batch
 and are averaged where they overlap - the result differs from an untiled forward (FDN's FFTs are global), so this is a
 feature of the reference being mirrored, not an optimisation.  scale = 1 (restoration, `opt['scale']`).
+
+blend="feather" is this project's own option beside that average: the tiles are weighted with linear ramps across their overlaps
+(feather_weights), so the merged frame has no step where one tile's coverage ends.  The default everywhere is the reference's average.
 """
 import ctypes
 import math
 
+import numpy as np
 import torch
 
 from . import FdnHipError, check, lib, stream
@@ -89,10 +93,71 @@ def split(x, crop_h, crop_w, overlap=0):
     return tiles, ij
 
 
-def merge(outs, ij, h, w):
-    """grids_inverse(): tiles (T,C,ch,cw) + origins -> (1,C,h,w), overlaps averaged."""
+BLENDS = ("average", "feather")
+
+
+def check_blend(blend):
+    if blend not in BLENDS:
+        raise ValueError(f"blend {blend!r}: 'average' (the reference's grids_inverse) or 'feather'")
+    return blend
+
+
+def _axis_ramps(origins, c):
+    """{origin: float64 [c]} for the tiles of length c along one axis: a linear ramp across the pixels shared with the previous tile and
+    with the next one, sampled at pixel centres, 1 elsewhere; where both ramps reach a pixel the smaller one holds"""
+    o = sorted(set(origins))
+    d = np.arange(c, dtype=np.float64)
+    ramps = {}
+    for k, ok in enumerate(o):
+        lo = max(0, o[k - 1] + c - ok) if k > 0 else 0
+        hi = max(0, ok + c - o[k + 1]) if k + 1 < len(o) else 0
+        wgt = np.ones(c, dtype=np.float64)
+        if lo > 0:
+            wgt[:lo] = np.minimum(wgt[:lo], (d[:lo] + 0.5) / lo)
+        if hi > 0:
+            wgt[c - hi:] = np.minimum(wgt[c - hi:], (c - d[c - hi:] - 0.5) / hi)
+        ramps[ok] = wgt
+    return ramps
+
+
+def feather_weights(idx, ch, cw):
+    """The weights of the feathered merge for the origins tile_origins returns -> (wy float32 [T][ch], wx float32 [T][cw]) on the CPU; tile
+    t weighs its pixel (dy, dx) with wy[t][dy] * wx[t][dx].  Per axis, with the unique origins sorted, a tile ramps up over the
+    lo = o[k-1] + c - o[k] pixels it shares with its predecessor, w(d) = (d + 0.5) / lo, and down over the hi = o[k] + c - o[k+1] pixels
+    it shares with its successor, w(d) = (c - d - 0.5) / hi; the weight is 1 elsewhere, and on a side at the frame's border or without
+    an overlapping neighbour.  Every weight is positive, and the ramps of two tiles that alone share a band sum to 1.  float64, rounded
+    once to float32."""
+    idx = [(int(i), int(j)) for i, j in idx]
+    rows, cols = sorted({i for i, _ in idx}), sorted({j for _, j in idx})
+    if not idx or len(idx) != len(rows) * len(cols) or set(idx) != {(i, j) for i in rows for j in cols}:
+        raise FdnHipError(f"feather_weights needs the full grid of origins that tile_origins returns, got {len(idx)} origins over "
+                          f"{len(rows)} rows and {len(cols)} columns")
+    if ch <= 0 or cw <= 0:
+        raise FdnHipError(f"tile {ch}x{cw} must be positive")
+    ry, rx = _axis_ramps(rows, ch), _axis_ramps(cols, cw)
+    wy = np.stack([ry[i] for i, _ in idx]).astype(np.float32)
+    wx = np.stack([rx[j] for _, j in idx]).astype(np.float32)
+    return torch.from_numpy(wy), torch.from_numpy(wx)
+
+
+def _feather_on_device(ij, ch, cw):
+    wy, wx = feather_weights(ij.cpu().tolist(), ch, cw)
+    return wy.to(ij.device).contiguous(), wx.to(ij.device).contiguous()
+
+
+def merge(outs, ij, h, w, blend="average"):
+    """grids_inverse(): tiles (T,C,ch,cw) + origins -> (1,C,h,w), overlaps averaged (blend "average", the reference) or weighted with
+    feather_weights ("feather": no step where a tile's coverage ends)."""
+    check_blend(blend)
     T, C, ch, cw = outs.shape
     out = torch.empty((1, C, h, w), device=outs.device, dtype=torch.float32)
+    if blend == "feather":
+        if tuple(ij.shape) != (T, 2):
+            raise FdnHipError(f"cannot merge tiles {tuple(outs.shape)} with origins {tuple(ij.shape)}")
+        wy, wx = _feather_on_device(ij, ch, cw)
+        check(lib().fdn_tiles_merge_w(_f32(outs, "outs"), _f32(out, "out"), ctypes.c_void_p(ij.data_ptr()), _f32(wy, "wy"), _f32(wx, "wx"),
+                                      T, C, h, w, ch, cw, stream()), "fdn_tiles_merge_w")
+        return out
     check(lib().fdn_tiles_merge(_f32(outs, "outs"), _f32(out, "out"), ctypes.c_void_p(ij.data_ptr()), T, C, h, w, ch, cw, stream()),
           "fdn_tiles_merge")
     return out
@@ -120,13 +185,19 @@ def split_u8(img_u8, crop_h, crop_w, bgr=True, overlap=0):
     return tiles, ij
 
 
-def merge_u8(outs, ij, h, w, bgr=True):
-    """grids_inverse() straight to the uint8 frame: tiles (T,3,ch,cw) + origins -> uint8 [h,w,3], overlaps averaged, then clamp(0,1),
-    *255, round half to even.  Bit for bit merge() followed by harness.postprocess."""
+def merge_u8(outs, ij, h, w, bgr=True, blend="average"):
+    """grids_inverse() straight to the uint8 frame: tiles (T,3,ch,cw) + origins -> uint8 [h,w,3], overlaps averaged or feathered (blend,
+    as merge takes it), then clamp(0,1), *255, round half to even.  Bit for bit merge() followed by harness.postprocess."""
+    check_blend(blend)
     T, C, ch, cw = outs.shape
     if C != 3 or ch > h or cw > w or tuple(ij.shape) != (T, 2) or ij.dtype != torch.int32 or not ij.is_cuda:
         raise FdnHipError(f"cannot merge tiles {tuple(outs.shape)} with origins {tuple(ij.shape)} into a {h}x{w} frame")
     out = torch.empty((h, w, 3), device=outs.device, dtype=torch.uint8)
+    if blend == "feather":
+        wy, wx = _feather_on_device(ij, ch, cw)
+        check(lib().fdn_tiles_merge_w_u8(_f32(outs, "outs"), _u8(out, "out"), ctypes.c_void_p(ij.data_ptr()), _f32(wy, "wy"), _f32(wx, "wx"),
+                                         T, h, w, ch, cw, int(bool(bgr)), stream()), "fdn_tiles_merge_w_u8")
+        return out
     check(lib().fdn_tiles_merge_u8(_f32(outs, "outs"), _u8(out, "out"), ctypes.c_void_p(ij.data_ptr()), T, h, w, ch, cw, int(bool(bgr)),
                                    stream()), "fdn_tiles_merge_u8")
     return out
@@ -185,18 +256,20 @@ def end_serving(dist, root=0):
 
 
 @torch.no_grad()
-def forward_tiled(net, lpnet, x, crop_h, crop_w, batch=8, ratio=None, overlap=0):
+def forward_tiled(net, lpnet, x, crop_h, crop_w, batch=8, ratio=None, overlap=0, blend="average"):
     """LPNet -> FDN on overlapping tiles of one padded image (crop sizes multiples of 32), merged like the reference.  ratio: [T,1]
-    (one per tile) or [1,1] (one for the frame) feeds FDN instead of LPNet's per-tile prediction; overlap as tile_origins takes it."""
+    (one per tile) or [1,1] (one for the frame) feeds FDN instead of LPNet's per-tile prediction; overlap as tile_origins takes it,
+    blend as merge takes it."""
+    check_blend(blend)
     if crop_h % 32 or crop_w % 32:
         raise FdnHipError("tile sizes must be multiples of 32 (three levels x 8x8 patches)")
     tiles, ij = split(x.contiguous(), crop_h, crop_w, overlap)
     if ratio is not None:
         if ratio.dim() != 2 or ratio.shape[1] != 1 or ratio.shape[0] not in (1, tiles.shape[0]):
             raise FdnHipError(f"ratio must be [1,1] or [{tiles.shape[0]},1], got {tuple(ratio.shape)}")
-        return merge(run_tiles(net, tiles, ratio.expand(tiles.shape[0], 1), batch), ij, x.shape[2], x.shape[3])
+        return merge(run_tiles(net, tiles, ratio.expand(tiles.shape[0], 1), batch), ij, x.shape[2], x.shape[3], blend)
     outs = torch.empty_like(tiles)
     for s in range(0, tiles.shape[0], batch):
         t = tiles[s:s + batch]
         outs[s:s + batch] = net(t, ratio_i=lpnet(t), device=t.device)[0]
-    return merge(outs, ij, x.shape[2], x.shape[3])
+    return merge(outs, ij, x.shape[2], x.shape[3], blend)

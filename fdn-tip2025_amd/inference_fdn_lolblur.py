@@ -10,9 +10,10 @@ Needs a ROCm GPU and the built libfdn_hip.so; there is no CPU fallback.
     python inference_fdn_lolblur.py --fdn FDN_lolblur.pth --lpnet LPNet_lolblur.pth --input 'frames/*.png' --output out/
 
 A frame larger than one forward can take (a 12 MP photo) runs with --tile HxW or --tile auto: overlapping tiles as the reference's
-val.grids cuts them, each through FDN, averaged where they overlap; the ratio comes from the whole frame (--tile-ratio frame) or from
-each tile (tile: the reference's semantics).  Under `python -m torch.distributed.run --nproc_per_node N` with --tile, rank 0 reads,
-splits, merges and writes, and the tiles of each frame are dealt to all N GPUs.
+val.grids cuts them, each through FDN, averaged where they overlap (--tile-blend feather: weighted with ramps across the overlaps, so that
+no step runs along the line where a tile ends; --tile-overlap sets the least width of those bands); the ratio comes from the whole frame
+(--tile-ratio frame) or from each tile (tile: the reference's semantics).  Under `python -m torch.distributed.run --nproc_per_node N`
+with --tile, rank 0 reads, splits, merges and writes, and the tiles of each frame are dealt to all N GPUs.
 """
 import argparse
 import glob
@@ -57,13 +58,16 @@ def tile_arg(s):
 
 
 def add_tile_args(ap, ratio_default="frame"):
-    """--tile / --tile-overlap, and --tile-ratio unless ratio_default is None (a driver whose ratio is fixed)"""
+    """--tile / --tile-overlap / --tile-blend, and --tile-ratio unless ratio_default is None (a driver whose ratio is fixed)"""
     ap.add_argument("--tile", type=tile_arg, default=None, metavar="HxW|auto|off",
                     help="run frames as overlapping tiles of this size (multiples of 32), merged by averaging; auto: 736x1280 tiles for "
                          "frames above 1088x1920 pixels only; default off")
     ap.add_argument("--tile-overlap", type=int, default=0, metavar="N",
                     help="least number of pixels neighbouring tiles share (default 0: the reference's rule, no overlap when a side is a "
                          "multiple of the tile)")
+    ap.add_argument("--tile-blend", choices=("average", "feather"), default="average",
+                    help="how overlapping tiles are merged: the reference's uniform average (default), or feather: linear ramps across "
+                         "each overlap, so no step where a tile's coverage ends (give it room with --tile-overlap)")
     if ratio_default is not None:
         ap.add_argument("--tile-ratio", choices=("frame", "tile"), default=ratio_default,
                         help=f"take the ratio from the whole frame or from each tile (default {ratio_default})")
@@ -82,6 +86,30 @@ def hint_large_frame(tile, h, w):
         _hinted = True
         print(f"note: a {h}x{w} frame is larger than a whole-frame forward is tested at (1088x1920 padded); --tile auto runs it in tiles",
               file=sys.stderr)
+
+
+_seam_hinted = False
+
+
+def hint_hard_seam(tile, blend, overlap, h, w):
+    """one line on stderr, once per run, when --tile-blend feather meets a frame axis whose neighbouring tiles share no pixel (a side that
+    is a multiple of the tile, with overlap 0): nothing to ramp across, the seam stays hard"""
+    global _seam_hinted
+    from fdn_hip.harness import resolve_tile
+    from fdn_hip.tiling import effective_crop, tile_origins
+    if blend != "feather" or _seam_hinted or tile is None:
+        return
+    crop = resolve_tile(tile, h, w)
+    if crop is None or h < 32 or w < 32:
+        return
+    ch, cw = effective_crop(h, w, *crop)
+    idx = tile_origins(h, w, ch, cw, overlap)
+    for name, org, c in (("rows", sorted({i for i, _ in idx}), ch), ("columns", sorted({j for _, j in idx}), cw)):
+        if any(a + c <= b for a, b in zip(org, org[1:])):
+            _seam_hinted = True
+            print(f"note: --tile-blend feather has no overlap to blend across along the {name} of a {h}x{w} frame cut into {ch}x{cw} tiles: "
+                  "that seam stays hard; --tile-overlap N makes neighbouring tiles share at least N pixels", file=sys.stderr)
+            return
 
 
 def run_driver(doc, build_models, ratio_mode="lolblur", fdn_keys="FDN checkpoint ({'params': state_dict}, 1503 keys)"):
@@ -121,7 +149,7 @@ def run_driver(doc, build_models, ratio_mode="lolblur", fdn_keys="FDN checkpoint
     lp = lp.to(dev).eval()
     lp.load_state_dict(load_params(a.lpnet), strict=True)
 
-    tile_kw = dict(ratio_from=a.tile_ratio, overlap=a.tile_overlap, batch=a.batch)
+    tile_kw = dict(ratio_from=a.tile_ratio, overlap=a.tile_overlap, batch=a.batch, blend=a.tile_blend)
 
     def serve(tiles, ratio):
         return tiling.run_tiles(net, tiles, ratio, a.batch)
@@ -135,6 +163,7 @@ def run_driver(doc, build_models, ratio_mode="lolblur", fdn_keys="FDN checkpoint
         """uint8 [B,h,w,3] -> uint8 [B,h,w,3]; with more than one rank the tiles of each frame go through all of them"""
         h, w = batch.shape[1:3]
         hint_large_frame(a.tile, h, w)
+        hint_hard_seam(a.tile, a.tile_blend, a.tile_overlap, h, w)
         if dist is None:
             return enhance_u8(net, lp, batch, bgr=False, ratio_mode=ratio_mode, tile=a.tile, **tile_kw)
         if resolve_tile(a.tile, h, w) is None:

@@ -5,7 +5,8 @@ repeated, ratio_i carries the grid, LPNet is not needed (its prediction only sup
 
     python inference_fdn_multi_r.py --fdn FDN_lolblur.pth --input frame.png --output multi_r/ [--start 0 --stop 1 --step 0.01]
 
---tile HxW|auto runs a frame larger than one forward can take as overlapping tiles (fdn_hip.harness.enhance_u8), one grid value at a time.
+--tile HxW|auto runs a frame larger than one forward can take as overlapping tiles (fdn_hip.harness.enhance_u8), one grid value at a time;
+--tile-blend feather merges them with ramps across their overlaps instead of the uniform average.
 """
 import argparse
 import os
@@ -16,7 +17,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from inference_fdn_lolblur import add_tile_args, hint_large_frame, load_params, read_rgb, write_rgb  # noqa: E402
+from inference_fdn_lolblur import add_tile_args, hint_hard_seam, hint_large_frame, load_params, read_rgb, write_rgb  # noqa: E402
 
 
 def sweep_values(start, stop, step):
@@ -51,12 +52,13 @@ def main():
     net.load_state_dict(load_params(a.fdn), strict=True)
     img = torch.from_numpy(read_rgb(a.input)).to(dev)
     hint_large_frame(a.tile, img.shape[0], img.shape[1])
+    hint_hard_seam(a.tile, a.tile_blend, a.tile_overlap, img.shape[0], img.shape[1])
     vals = sweep_values(a.start, a.stop, a.step)
     for c0 in range(0, len(vals), a.batch):
         chunk = vals[c0:c0 + a.batch]
         ratio = torch.tensor(chunk, dtype=torch.float32, device=dev).view(-1, 1)
         out = enhance_u8(net, None, img.unsqueeze(0).expand(len(chunk), -1, -1, -1).contiguous(), bgr=False, ratio_mode="fixed", ratio=ratio,
-                         tile=a.tile, overlap=a.tile_overlap, batch=a.batch)
+                         tile=a.tile, overlap=a.tile_overlap, batch=a.batch, blend=a.tile_blend)
         for v, o in zip(chunk, out.cpu().numpy()):
             write_rgb(os.path.join(a.output, output_name(v)), o)
     print(f"{len(vals)} ratios -> {a.output}")

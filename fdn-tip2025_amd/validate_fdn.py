@@ -13,7 +13,8 @@ scores take one small copy per batch.  Needs a ROCm GPU and the built libfdn_hip
 
 --tile HxW plays the reference's `val.grids` with crop_size_h / crop_size_w (:261-339, :737-743): every frame is cut into overlapping tiles,
 the ratio is taken per tile as the reference does after grids() (--tile-ratio tile, the default here; frame: one ratio from the whole
-frame), and the merged 8-bit frame is scored.  The csv then holds one ratio per tile, joined by ';'.
+frame), and the merged 8-bit frame is scored.  The csv then holds one ratio per tile, joined by ';'.  --tile-blend feather merges the
+tiles with ramps across their overlaps instead of the reference's average (not what the reference scores).
 """
 import argparse
 import glob
@@ -79,7 +80,7 @@ def main(argv=None):
     a = parse_args(argv)
     import torch
     from fdn_hip.harness import validate_u8
-    from inference_fdn_lolblur import hint_large_frame, load_params, write_rgb
+    from inference_fdn_lolblur import hint_hard_seam, hint_large_frame, load_params, write_rgb
     from basicsr.models.archs.LPNet_arch import I_predict_net
     if a.variant == "lolblur":
         from basicsr.models.archs.FDN_arch import FDN as Net
@@ -103,8 +104,9 @@ def main(argv=None):
         for idx, lqs, gts in decoded_groups(a.pairs, a.batch, pool):
             lq, gt = torch.from_numpy(lqs).to(dev), torch.from_numpy(gts).to(dev)
             hint_large_frame(a.tile, lqs.shape[1], lqs.shape[2])
+            hint_hard_seam(a.tile, a.tile_blend, a.tile_overlap, lqs.shape[1], lqs.shape[2])
             out, p, s, r = validate_u8(net, lp, lq, gt, ratio_mode=mode, crop_border=a.crop_border, bgr=False, tile=a.tile,
-                                       ratio_from=a.tile_ratio, overlap=a.tile_overlap, batch=a.batch)
+                                       ratio_from=a.tile_ratio, overlap=a.tile_overlap, batch=a.batch, blend=a.tile_blend)
             r = r.reshape(r.shape[0], -1).cpu().tolist()              # one ratio per frame, or one per tile of a tiled frame
             frames = out.cpu().numpy() if a.dest else None
             for k, i in enumerate(idx):

@@ -381,6 +381,19 @@ int fdn_tiles_gather_u8(const unsigned char* img, float* tiles, const int* ij, i
                         fdn_stream_t stream);
 int fdn_tiles_merge_u8(const float* tiles, unsigned char* out, const int* ij, int T, int h, int w, int ch, int cw, int swap_rb,
                        fdn_stream_t stream);
+/* Added under ABI 21 (an addition: no signature above changes).  The feathered merge, which the reference does not have: where tiles
+ * overlap, the uniform average above steps by half their disagreement at the line where one tile's coverage ends; here tile t weighs its
+ * pixel (dy, dx) with wy[t][dy] * wx[t][dx] (the product formed in fp32), wy device float [T][ch] and wx device float [T][cw], all
+ * positive - fdn_hip.tiling.feather_weights builds linear ramps across each overlap, 1 elsewhere.  Same ij, T < 65536, ch <= H, cw <= W.
+ * fdn_tiles_merge_w   : tiles [T][C][ch][cw] -> out [C][H][W] = (sum of w_t x_t) / (sum of w_t) over the tiles covering the pixel, in
+ *   tile order, every product, add and the division rounded once in fp32 (no FMA contraction).
+ * fdn_tiles_merge_w_u8: tiles [T][3][ch][cw] -> out [h][w][3] uint8 = rintf(clamp(that quotient, 0, 1) * 255): bit for bit
+ *   fdn_tiles_merge_w then fdn_post_u8(H = h, W = w) for finite inputs; swap_rb = 1 writes BGR.  With all weights 1 both equal the
+ *   unweighted pair bit for bit.  Every pixel must be covered by a tile. */
+int fdn_tiles_merge_w(const float* tiles, float* out, const int* ij, const float* wy, const float* wx, int T, int C, int H, int W, int ch,
+                      int cw, fdn_stream_t stream);
+int fdn_tiles_merge_w_u8(const float* tiles, unsigned char* out, const int* ij, const float* wy, const float* wx, int T, int h, int w,
+                         int ch, int cw, int swap_rb, fdn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Validation metrics on the GPU (basicsr/metrics/psnr_ssim.py:8-73, :163-197).

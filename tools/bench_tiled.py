@@ -1,8 +1,9 @@
 """Tiled inference timing: one synthetic uint8 frame (default 3000 x 4000, 20 tiles of 736 x 1280 under tile="auto") through
 fdn_hip.harness.enhance_u8 with the tamed synthetic weights of the test suite (the time does not depend on the values), wall clock around
 a synchronised call and torch.cuda.max_memory_allocated; and the two uint8 <-> tile kernels of ABI 21 against the four-call compositions
-they replace (fdn_pre_u8 + fdn_tiles_gather, fdn_tiles_merge + fdn_post_u8) at the same size, HIP events around the launches.  The
-shader clock is sampled while the frame runs (bench.GpuSensors).  Prints one JSON line; --out writes it too.
+they replace (fdn_pre_u8 + fdn_tiles_gather, fdn_tiles_merge + fdn_post_u8) at the same size, HIP events around the launches; and the
+feathered uint8 merge (fdn_tiles_merge_w_u8) beside the averaging one.  The shader clock is sampled while the frame runs
+(bench.GpuSensors).  Prints one JSON line; --out writes it too.
 
     python tools/bench_tiled.py --reps 3 --out profiles/tiled_bench.json
 """
@@ -103,6 +104,30 @@ def main():
                      "fdn_pre_u8 + fdn_tiles_gather": gpu_ms(four_call_in, a.kernel_reps), "bit_equal": same_in}
     res["merge"] = {"fdn_tiles_merge_u8": gpu_ms(lambda: tiling.merge_u8(outs, ij, h, w, bgr=False), a.kernel_reps),
                     "fdn_tiles_merge + fdn_post_u8": gpu_ms(four_call_out, a.kernel_reps), "bit_equal": same_out}
+
+    # the feathered merge beside the average: the launch alone (weights already on the device), and tiling.merge_u8(blend="feather") as the
+    # route calls it, which builds the weight vectors on the host and copies them for every frame
+    idx = ij.cpu().tolist()
+    wy, wx = (t.to(dev).contiguous() for t in tiling.feather_weights(idx, tiles.shape[2], tiles.shape[3]))
+    out_w = torch.empty((h, w, 3), device=dev, dtype=torch.uint8)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+
+    def feather_launch():
+        fdn_hip.check(fdn_hip.lib().fdn_tiles_merge_w_u8(ptr(outs), ptr(out_w), ptr(ij), ptr(wy), ptr(wx), len(idx), h, w, tiles.shape[2],
+                                                         tiles.shape[3], 0, fdn_hip.stream()), "fdn_tiles_merge_w_u8")
+    out_a = torch.empty_like(out_w)
+
+    def average_launch():
+        fdn_hip.check(fdn_hip.lib().fdn_tiles_merge_u8(ptr(outs), ptr(out_a), ptr(ij), len(idx), h, w, tiles.shape[2], tiles.shape[3], 0,
+                                                       fdn_hip.stream()), "fdn_tiles_merge_u8")
+    feather_launch()
+    same_w = torch.equal(out_w, harness.postprocess(tiling.merge(outs, ij, h, w, blend="feather"), h, w, bgr=False)[0])
+    res["merge_feather"] = {"fdn_tiles_merge_w_u8 (launch)": gpu_ms(feather_launch, a.kernel_reps),
+                            "fdn_tiles_merge_u8 (launch)": gpu_ms(average_launch, a.kernel_reps),
+                            "tiling.merge_u8(blend='feather') with host weights": gpu_ms(lambda: tiling.merge_u8(outs, ij, h, w, bgr=False, blend="feather"),
+                                                                                         a.kernel_reps),
+                            "bytes_differing_from_average": int((out_w != tiling.merge_u8(outs, ij, h, w, bgr=False)).sum()),
+                            "bit_equal_to_fdn_tiles_merge_w + fdn_post_u8": same_w}
     res["device"] = torch.cuda.get_device_name(0)
     print(json.dumps(res))
     if a.out:
