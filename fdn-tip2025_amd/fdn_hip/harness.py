@@ -18,8 +18,14 @@ PSNR / SSIM of the uint8 result against the uint8 ground truth.
 With `tile`, a frame larger than one forward can take goes uint8 -> tiling.split_u8 -> tiling.run_tiles -> tiling.merge_u8 -> uint8 (the
 reference's val.grids, image_restoration_model.py:261-339, :737-743), one frame at a time; no fp32 frame exists except the one a
 frame-level ratio is taken from.  blend="feather" merges the tiles with ramps across their overlaps instead of the reference's average.
+
+Video frames (no reference counterpart): preprocess_yuv420 / postprocess_yuv420 / enhance_yuv420 are the same walk between Y'CbCr 4:2:0
+frames as a decoder hands them out (VideoFormat: yuv420p, nv12, yuv420p10le) and the same forward, through fdn_pre_yuv420 /
+fdn_post_yuv420 (include/fdn_video.h): codec samples -> fp32 -> codec samples, rounded once.
 """
 import ctypes
+from dataclasses import dataclass
+
 import torch
 
 from . import lib, check, stream, FdnHipError
@@ -119,6 +125,43 @@ def _per_tile(fn, tiles, batch):
     return torch.cat([fn(tiles[s:s + batch]) for s in range(0, tiles.shape[0], batch)])
 
 
+def frame_ratio(lpnet, x, ratio_mode, x_gt=None):
+    """The ratio [B,1] of reflect-padded fp32 frames x [B,3,H,W] as the untiled call feeds it: LPNet ("lolblur"), mean(gray) / LPNet
+    ("lolv1") or gt_ratio against the padded ground truth x_gt ("gt")."""
+    if ratio_mode == "gt":
+        return gt_ratio(x, x_gt)
+    if ratio_mode == "lolblur":
+        return lpnet(x)
+    return lolv1_ratio(x, lpnet(x))
+
+
+def _tile_ratio(lpnet, tiles, ratio_mode, ratio_from, ratio, batch, frame, gt=None):
+    """tile_ratio on fp32 frames, whatever they were converted from: frame() -> the reflect-padded fp32 frame [1,3,H,W]; gt, for ratio_mode
+    "gt", a pair of such callables: the ground truth padded, and whole and unpadded."""
+    if ratio_from not in ("frame", "tile"):
+        raise ValueError(f"ratio_from {ratio_from!r}")
+    T = tiles.shape[0]
+    if ratio_mode == "fixed":
+        if ratio is None or ratio.dim() != 2 or ratio.shape[1] != 1 or ratio.shape[0] not in (1, T):
+            raise FdnHipError(f"ratio_mode 'fixed' on {T} tiles needs ratio [1,1] or [{T},1]")
+        return ratio.to(device=tiles.device, dtype=torch.float32).expand(T, 1).contiguous()
+    if ratio_mode == "gt" and gt is None:
+        raise FdnHipError("ratio_mode 'gt' needs the ground-truth frame")
+    if ratio_mode != "gt" and lpnet is None:
+        raise FdnHipError(f"ratio_mode {ratio_mode!r} needs lpnet")
+    if ratio_from == "frame":
+        r = frame_ratio(lpnet, frame(), ratio_mode, gt[0]() if ratio_mode == "gt" else None)
+        return r.expand(T, 1).contiguous()
+    if ratio_mode == "lolblur":
+        return _per_tile(lpnet, tiles, batch)
+    if ratio_mode == "lolv1":
+        return _per_tile(lambda t: lolv1_ratio(t, lpnet(t)), tiles, batch)
+    high = _gray_mean(gt[1]())
+    if bool((high == 0).any()):
+        raise FdnHipError("gt_ratio: a ground-truth image has gray mean 0")
+    return _per_tile(_gray_mean, tiles, batch) / high
+
+
 def tile_ratio(lpnet, img_u8, tiles, ratio_mode, ratio_from, bgr=True, ratio=None, gt_u8=None, batch=8):
     """The ratio [T,1] that FDN takes on the tiles of one uint8 frame [h,w,3].
     ratio_from "frame": what the untiled call feeds - LPNet / mean(gray) / gt_ratio on the reflect-padded whole frame (LPNet's tensors are
@@ -127,34 +170,20 @@ def tile_ratio(lpnet, img_u8, tiles, ratio_mode, ratio_from, bgr=True, ratio=Non
     (image_restoration_model.py:578-586, :650-654): LPNet / mean(gray) per tile; "gt" is mean(gray(tile)) / mean(gray(ground truth)) with
     the ground truth whole and unpadded (tiles are multiples of 32, so :583-586 pad nothing).
     "fixed": the caller's `ratio`, [1,1] for the frame or [T,1]."""
-    if ratio_from not in ("frame", "tile"):
-        raise ValueError(f"ratio_from {ratio_from!r}")
-    T = tiles.shape[0]
+    gt = None if gt_u8 is None else (lambda: preprocess(gt_u8, bgr=bgr)[0], lambda: _frame_f32(gt_u8, bgr))
+    return _tile_ratio(lpnet, tiles, ratio_mode, ratio_from, ratio, batch, lambda: preprocess(img_u8, bgr=bgr)[0], gt)
+
+
+def _forward(net, lpnet, x, ratio_mode, ratio):
+    """LPNet -> FDN on reflect-padded frames x [B,3,H,W] -> result [B,3,H,W]; ratio_mode / ratio as enhance_u8 takes them"""
     if ratio_mode == "fixed":
-        if ratio is None or ratio.dim() != 2 or ratio.shape[1] != 1 or ratio.shape[0] not in (1, T):
-            raise FdnHipError(f"ratio_mode 'fixed' on {T} tiles needs ratio [1,1] or [{T},1]")
-        return ratio.to(device=tiles.device, dtype=torch.float32).expand(T, 1).contiguous()
-    if ratio_mode == "gt" and gt_u8 is None:
-        raise FdnHipError("ratio_mode 'gt' needs the ground-truth frame")
-    if ratio_mode != "gt" and lpnet is None:
-        raise FdnHipError(f"ratio_mode {ratio_mode!r} needs lpnet")
-    if ratio_from == "frame":
-        x = preprocess(img_u8, bgr=bgr)[0]
-        if ratio_mode == "gt":
-            r = gt_ratio(x, preprocess(gt_u8, bgr=bgr)[0])
-        elif ratio_mode == "lolblur":
-            r = lpnet(x)
-        else:
-            r = lolv1_ratio(x, lpnet(x))
-        return r.expand(T, 1).contiguous()
+        if ratio is None or tuple(ratio.shape) != (x.shape[0], 1):
+            raise FdnHipError(f"ratio_mode 'fixed' needs ratio [B,1] for B = {x.shape[0]}")
+        return net(x, ratio_i=ratio.to(device=x.device, dtype=torch.float32).contiguous(), device=x.device)[0]
     if ratio_mode == "lolblur":
-        return _per_tile(lpnet, tiles, batch)
-    if ratio_mode == "lolv1":
-        return _per_tile(lambda t: lolv1_ratio(t, lpnet(t)), tiles, batch)
-    high = _gray_mean(_frame_f32(gt_u8, bgr))
-    if bool((high == 0).any()):
-        raise FdnHipError("gt_ratio: a ground-truth image has gray mean 0")
-    return _per_tile(_gray_mean, tiles, batch) / high
+        from .pipeline import run
+        return run(net, lpnet, x)                  # hipGraph replay for small frames, the eager forward otherwise
+    return net(x, ratio_i=lolv1_ratio(x, lpnet(x)), device=x.device)[0]
 
 
 @torch.no_grad()
@@ -182,17 +211,7 @@ def enhance_u8(net, lpnet, img_u8, bgr=True, ratio_mode="lolblur", ratio=None, t
                                                 blend=blend)[0]
                             for b in range(img_u8.shape[0])])
     x, h, w = preprocess(img_u8, bgr=bgr)
-    if ratio_mode == "fixed":
-        if ratio is None or tuple(ratio.shape) != (x.shape[0], 1):
-            raise FdnHipError(f"ratio_mode 'fixed' needs ratio [B,1] for B = {x.shape[0]}")
-        result = net(x, ratio_i=ratio.to(device=x.device, dtype=torch.float32).contiguous(), device=x.device)[0]
-    elif ratio_mode == "lolblur":
-        from .pipeline import run
-        result = run(net, lpnet, x)                # hipGraph replay for small frames, the eager forward otherwise
-    else:
-        ratio = lolv1_ratio(x, lpnet(x))
-        result = net(x, ratio_i=ratio, device=x.device)[0]
-    return postprocess(result.contiguous(), h, w, bgr=bgr)
+    return postprocess(_forward(net, lpnet, x, ratio_mode, ratio).contiguous(), h, w, bgr=bgr)
 
 
 @torch.no_grad()
@@ -257,3 +276,132 @@ def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=Tr
     out = postprocess(net(x, ratio_i=ratio, device=x.device)[0].contiguous(), h, w, bgr=bgr)
     psnr, ssim = calculate_psnr_ssim_u8(out, gt_u8, crop_border=crop_border, bgr=bgr)
     return out, psnr, ssim, ratio
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Video frames: Y'CbCr 4:2:0 as decoders hand it out (include/fdn_video.h)
+# ---------------------------------------------------------------------------------------------------------------------------------
+_PIX_FMTS = {"yuv420p": (0, 8), "nv12": (1, 8), "yuv420p10le": (0, 10)}       # ffmpeg's names -> (layout, bits)
+_MATRICES = {"bt601": 0, "bt709": 1}
+_CHROMA_LOCS = {"left": 0, "center": 1}
+
+
+@dataclass(frozen=True)
+class VideoFormat:
+    """How the samples of a 4:2:0 frame are laid out and what they mean.  pix_fmt: yuv420p (planar 8 bit), nv12 (semi-planar 8 bit) or
+    yuv420p10le (planar, 10 bits in little-endian 16-bit words); matrix: bt601 | bt709; full_range: codes 0 .. 2^bits - 1 instead of the
+    limited 16 .. 235 / 240 (x 4 at 10 bit); chroma_loc: left (H.264 / HEVC default) | center (JPEG / MPEG-1)."""
+    pix_fmt: str = "yuv420p"
+    matrix: str = "bt709"
+    full_range: bool = False
+    chroma_loc: str = "left"
+
+    def __post_init__(self):
+        if self.pix_fmt not in _PIX_FMTS:
+            raise ValueError(f"pix_fmt {self.pix_fmt!r}: one of {', '.join(_PIX_FMTS)}")
+        if self.matrix not in _MATRICES:
+            raise ValueError(f"matrix {self.matrix!r}: bt601 or bt709")
+        if self.chroma_loc not in _CHROMA_LOCS:
+            raise ValueError(f"chroma_loc {self.chroma_loc!r}: left or center")
+
+    @property
+    def layout(self):
+        return _PIX_FMTS[self.pix_fmt][0]
+
+    @property
+    def bits(self):
+        return _PIX_FMTS[self.pix_fmt][1]
+
+    @property
+    def dtype(self):
+        """the sample type postprocess_yuv420 writes: uint8, or int16 for 10 bit (the codes 0 .. 1023 read the same as uint16)"""
+        return torch.uint8 if self.bits == 8 else torch.int16
+
+    @property
+    def sample_bytes(self):
+        return 1 if self.bits == 8 else 2
+
+    def frame_samples(self, h, w):
+        if h <= 0 or w <= 0 or h % 2 or w % 2:
+            raise FdnHipError(f"a 4:2:0 frame needs even, positive sides, got {h}x{w}")
+        return h * w * 3 // 2
+
+    def _codes(self):
+        return self.layout, self.bits, _MATRICES[self.matrix], int(bool(self.full_range)), _CHROMA_LOCS[self.chroma_loc]
+
+
+def _yuv_frames(frames, h, w, fmt):
+    """frames as preprocess_yuv420 takes them -> [B, frame_samples]; dtype and size are judged before where the tensor lives"""
+    ok = (torch.uint8,) if fmt.bits == 8 else (torch.int16, torch.uint16)
+    if not isinstance(frames, torch.Tensor) or frames.dtype not in ok:
+        raise FdnHipError(f"{fmt.pix_fmt} frames must be {' or '.join(str(d) for d in ok)} tensors, got {getattr(frames, 'dtype', type(frames))}")
+    if frames.dim() == 1:
+        frames = frames.unsqueeze(0)
+    n = fmt.frame_samples(h, w)
+    if frames.dim() != 2 or frames.shape[1] != n or frames.shape[0] < 1:
+        raise FdnHipError(f"expected {fmt.pix_fmt} frames [B, {n}] for {h}x{w}, got {tuple(frames.shape)}")
+    return frames
+
+
+def _yuv_ptr(t, what):
+    if not t.is_cuda or not t.is_contiguous():
+        raise FdnHipError(f"{what} must be a contiguous ROCm tensor")
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def preprocess_yuv420(frames, h, w, fmt, pad=True):
+    """4:2:0 frames [B, h*w*3/2] (uint8, or int16 / uint16 for 10 bit) on the GPU -> (fp32 [B,3,H,W] R'G'B' in [0,1], h, w): chroma
+    interpolated to the luma grid, converted with fmt's matrix and range, clamped to the gamut, reflect-padded bottom / right to the x32
+    grid like preprocess - or not at all with pad=False (H, W = h, w: the frame the tiled route cuts its tiles from)."""
+    frames = _yuv_frames(frames, h, w, fmt)
+    H, W = padded_size(h, w) if pad else (h, w)
+    if H - h >= h or W - w >= w:
+        raise FdnHipError(f"reflect padding {h}x{w} -> {H}x{W} needs pad < size (F.pad raises the same way)")
+    src = _yuv_ptr(frames, "frames")
+    out = torch.empty((frames.shape[0], 3, H, W), device=frames.device, dtype=torch.float32)
+    check(lib().fdn_pre_yuv420(src, ctypes.c_void_p(out.data_ptr()), frames.shape[0], h, w, H, W, *fmt._codes(), stream()), "fdn_pre_yuv420")
+    return out, h, w
+
+
+def postprocess_yuv420(result, h, w, fmt):
+    """fp32 [B,3,H,W] -> 4:2:0 frames [B, h*w*3/2] of fmt.dtype: crop, clamp(0,1), R'G'B' -> Y'CbCr, chroma downsampled from the cropped
+    region, scaled to fmt's range, rounded half to even."""
+    if not result.is_cuda or result.dtype != torch.float32 or not result.is_contiguous() or result.dim() != 4:
+        raise FdnHipError("result must be a contiguous float32 ROCm tensor [B,3,H,W]")
+    B, C, H, W = result.shape
+    if C != 3 or h > H or w > W:
+        raise FdnHipError(f"cannot crop {h}x{w} out of {tuple(result.shape)}")
+    out = torch.empty((B, fmt.frame_samples(h, w)), device=result.device, dtype=fmt.dtype)
+    check(lib().fdn_post_yuv420(ctypes.c_void_p(result.data_ptr()), _yuv_ptr(out, "out"), B, h, w, H, W, *fmt._codes(), stream()),
+          "fdn_post_yuv420")
+    return out
+
+
+@torch.no_grad()
+def enhance_yuv420(net, lpnet, frames, h, w, fmt, ratio_mode="lolblur", ratio=None, tile=None, ratio_from="frame", overlap=0, batch=8,
+                   blend="average"):
+    """4:2:0 frames in -> 4:2:0 frames out, shaped and typed like the input, through LPNet -> FDN: enhance_u8 for video.  frames and fmt
+    as preprocess_yuv420 takes them; every other keyword means what it means in enhance_u8.  Untiled, the batch goes through one forward;
+    with a tile that resolve_tile turns into a crop, frame by frame: preprocess_yuv420(pad=False) -> tiling.split -> the ratio (from the
+    reflect-padded frame, or per tile) -> tiling.run_tiles -> tiling.merge(blend) -> postprocess_yuv420."""
+    from . import tiling
+    if ratio_mode not in ("lolblur", "lolv1", "fixed"):
+        raise ValueError(f"ratio_mode {ratio_mode!r}")
+    tiling.check_blend(blend)
+    frames = _yuv_frames(frames, h, w, fmt)
+    B = frames.shape[0]
+    crop = resolve_tile(tile, h, w)
+    if crop is None:
+        x = preprocess_yuv420(frames, h, w, fmt)[0]
+        return postprocess_yuv420(_forward(net, lpnet, x, ratio_mode, ratio).contiguous(), h, w, fmt).view(frames.dtype)
+    if ratio_mode == "fixed" and (ratio is None or ratio.shape[0] != B):
+        raise FdnHipError(f"ratio_mode 'fixed' needs ratio [B,1] or [B,T,1] for B = {B}")
+    ch, cw = tiling.effective_crop(h, w, *crop)
+    out = []
+    for b in range(B):
+        frame = frames[b:b + 1]
+        tiles, ij = tiling.split(preprocess_yuv420(frame, h, w, fmt, pad=False)[0], ch, cw, overlap)
+        r = _tile_ratio(lpnet, tiles, ratio_mode, ratio_from, None if ratio is None else ratio[b].reshape(-1, 1), batch,
+                        lambda: preprocess_yuv420(frame, h, w, fmt)[0])
+        out.append(postprocess_yuv420(tiling.merge(tiling.run_tiles(net, tiles, r, batch), ij, h, w, blend), h, w, fmt))
+    return torch.cat(out).view(frames.dtype)
