@@ -21,7 +21,8 @@ frame-level ratio is taken from.  blend="feather" merges the tiles with ramps ac
 
 Video frames (no reference counterpart): preprocess_yuv420 / postprocess_yuv420 / enhance_yuv420 are the same walk between Y'CbCr 4:2:0
 frames as a decoder hands them out (VideoFormat: yuv420p, nv12, yuv420p10le) and the same forward, through fdn_pre_yuv420 /
-fdn_post_yuv420 (include/fdn_video.h): codec samples -> fp32 -> codec samples, rounded once.
+fdn_post_yuv420 (include/fdn_video.h): codec samples -> fp32 -> codec samples, rounded once.  enhance_yuv420(temporal=RatioFilter) filters
+the ratio across the frames of a stream (fdn_hip.temporal, include/fdn_temporal.h).
 """
 import ctypes
 from dataclasses import dataclass
@@ -379,20 +380,34 @@ def postprocess_yuv420(result, h, w, fmt):
 
 @torch.no_grad()
 def enhance_yuv420(net, lpnet, frames, h, w, fmt, ratio_mode="lolblur", ratio=None, tile=None, ratio_from="frame", overlap=0, batch=8,
-                   blend="average"):
+                   blend="average", temporal=None):
     """4:2:0 frames in -> 4:2:0 frames out, shaped and typed like the input, through LPNet -> FDN: enhance_u8 for video.  frames and fmt
     as preprocess_yuv420 takes them; every other keyword means what it means in enhance_u8.  Untiled, the batch goes through one forward;
     with a tile that resolve_tile turns into a crop, frame by frame: preprocess_yuv420(pad=False) -> tiling.split -> the ratio (from the
-    reflect-padded frame, or per tile) -> tiling.run_tiles -> tiling.merge(blend) -> postprocess_yuv420."""
+    reflect-padded frame, or per tile) -> tiling.run_tiles -> tiling.merge(blend) -> postprocess_yuv420.
+    temporal: None, or the fdn_hip.temporal.RatioFilter of the stream these frames continue: what FDN would be fed per frame (frame_ratio:
+    LPNet's prediction, or mean(gray) / LPNet for "lolv1") is filtered across the frames on the device, then fed as the "fixed" mode
+    feeds a ratio; with a tile the frame's filtered ratio goes to every tile (ratio_from "frame" only)."""
     from . import tiling
     if ratio_mode not in ("lolblur", "lolv1", "fixed"):
         raise ValueError(f"ratio_mode {ratio_mode!r}")
     tiling.check_blend(blend)
+    if temporal is not None:
+        if ratio_mode == "fixed":
+            raise ValueError("temporal with ratio_mode 'fixed': a ratio the caller sets is not filtered")
+        if ratio_from != "frame":
+            raise ValueError(f"temporal with ratio_from {ratio_from!r}: the filter keeps one ratio per frame, not per tile")
+        if not temporal.matches(h, w, fmt.bits):
+            raise ValueError(f"temporal filter is for {temporal.h}x{temporal.w} {temporal.bits}-bit frames, these are {h}x{w} {fmt.bits}-bit")
+        if lpnet is None:
+            raise FdnHipError(f"ratio_mode {ratio_mode!r} needs lpnet")
     frames = _yuv_frames(frames, h, w, fmt)
     B = frames.shape[0]
     crop = resolve_tile(tile, h, w)
     if crop is None:
         x = preprocess_yuv420(frames, h, w, fmt)[0]
+        if temporal is not None:
+            ratio_mode, ratio = "fixed", temporal.step(frames, frame_ratio(lpnet, x, ratio_mode).contiguous())
         return postprocess_yuv420(_forward(net, lpnet, x, ratio_mode, ratio).contiguous(), h, w, fmt).view(frames.dtype)
     if ratio_mode == "fixed" and (ratio is None or ratio.shape[0] != B):
         raise FdnHipError(f"ratio_mode 'fixed' needs ratio [B,1] or [B,T,1] for B = {B}")
@@ -401,7 +416,11 @@ def enhance_yuv420(net, lpnet, frames, h, w, fmt, ratio_mode="lolblur", ratio=No
     for b in range(B):
         frame = frames[b:b + 1]
         tiles, ij = tiling.split(preprocess_yuv420(frame, h, w, fmt, pad=False)[0], ch, cw, overlap)
-        r = _tile_ratio(lpnet, tiles, ratio_mode, ratio_from, None if ratio is None else ratio[b].reshape(-1, 1), batch,
-                        lambda: preprocess_yuv420(frame, h, w, fmt)[0])
+        if temporal is not None:
+            r = frame_ratio(lpnet, preprocess_yuv420(frame, h, w, fmt)[0], ratio_mode).contiguous()
+            r = temporal.step(frame, r).expand(tiles.shape[0], 1).contiguous()
+        else:
+            r = _tile_ratio(lpnet, tiles, ratio_mode, ratio_from, None if ratio is None else ratio[b].reshape(-1, 1), batch,
+                            lambda: preprocess_yuv420(frame, h, w, fmt)[0])
         out.append(postprocess_yuv420(tiling.merge(tiling.run_tiles(net, tiles, r, batch), ij, h, w, blend), h, w, fmt))
     return torch.cat(out).view(frames.dtype)

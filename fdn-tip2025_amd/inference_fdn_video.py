@@ -10,7 +10,8 @@ so a frame goes from the decoder's samples straight to fp32 and back, rounded on
 
 IN / OUT: paths, `-` = stdin / stdout (binary); every message goes to stderr.  The output has the input's container and format: for Y4M
 the input's header line is written back verbatim and `FRAME` precedes each frame.  Frames larger than one forward can take run with
---tile, as in the image drivers.  One process, one GPU.  Needs a ROCm GPU and the built libfdn_hip.so; there is no CPU fallback.
+--tile, as in the image drivers.  --ratio-smooth ALPHA filters the ratio FDN is fed across the frames (fdn_hip.temporal: against the flicker
+of a ratio predicted frame by frame), --scene-cut FRACTION sets where it starts afresh.  One process, one GPU.  Needs a ROCm GPU and the built libfdn_hip.so; there is no CPU fallback.
 """
 import argparse
 import os
@@ -289,7 +290,20 @@ def stream_video(a, reader, dst, fmt, w, h, y4m_line, enhance, dev):
     return done
 
 
-def main():
+def unit_fraction(low_open):
+    """argparse type of a value in (0, 1] (low_open) or [0, 1]"""
+    def parse(s):
+        try:
+            v = float(s)
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"{s!r} is not a number")
+        if not (0.0 < v <= 1.0 if low_open else 0.0 <= v <= 1.0):
+            raise argparse.ArgumentTypeError(f"{s!r} is not in {'(0, 1]' if low_open else '[0, 1]'}")
+        return v
+    return parse
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--fdn", required=True, help="FDN checkpoint ({'params': state_dict})")
     ap.add_argument("--lpnet", required=True, help="LPNet checkpoint")
@@ -305,12 +319,26 @@ def main():
     ap.add_argument("--chroma-loc", choices=("left", "center"), default=None, help="default: the Y4M header's, left for raw")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--ratio-smooth", type=unit_fraction(True), default=None, metavar="ALPHA",
+                    help="filter the ratio FDN is fed across frames against flicker: ratio = previous + ALPHA * (this frame's - previous), "
+                         "ALPHA in (0, 1], started afresh at a scene cut; 1 filters nothing but still counts cuts (default: off, every "
+                         "frame on its own)")
+    ap.add_argument("--scene-cut", type=unit_fraction(False), default=0.3, metavar="FRACTION",
+                    help="with --ratio-smooth: a scene cut is where more than this fraction of the pixels changed their luma bin (of 256) "
+                         "against the frame before; 1 = never (default 0.3)")
     add_tile_args(ap)
-    a = ap.parse_args()
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise SystemExit("inference_fdn_video.py runs as one process on one GPU: WORLD_SIZE > 1 is not supported")
+    a = ap.parse_args(argv)
     if a.batch < 1:
         ap.error("--batch must be at least 1")
+    if a.ratio_smooth is not None and a.tile_ratio != "frame":
+        ap.error("--ratio-smooth filters one ratio per frame: it needs --tile-ratio frame")
+    return a
+
+
+def main():
+    a = parse_args()
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("inference_fdn_video.py runs as one process on one GPU: WORLD_SIZE > 1 is not supported")
 
     src, dst = open_streams(a)
     reader, fmt, w, h, y4m_line = open_video(a, src)
@@ -331,9 +359,14 @@ def main():
     hint_large_frame(a.tile, h, w)
     hint_hard_seam(a.tile, a.tile_blend, a.tile_overlap, h, w)
 
+    smooth = None
+    if a.ratio_smooth is not None:                                       # one filter per run: the run is one stream of frames
+        from fdn_hip.temporal import RatioFilter
+        smooth = RatioFilter(h, w, fmt.bits, a.ratio_smooth, cut=a.scene_cut, device=dev)
+
     def enhance(frames):
         return enhance_yuv420(net, lp, frames, h, w, fmt, ratio_mode=a.model, tile=a.tile, ratio_from=a.tile_ratio, overlap=a.tile_overlap,
-                              batch=a.batch, blend=a.tile_blend)
+                              batch=a.batch, blend=a.tile_blend, temporal=smooth)
 
     try:
         done = stream_video(a, reader, dst, fmt, w, h, y4m_line, enhance, dev)
@@ -341,7 +374,7 @@ def main():
         dst.flush()
         raise SystemExit(f"inference_fdn_video.py: {e}; {reader.frames} complete frames -> {a.output}")
     dst.close()
-    say(f"{done} frames -> {a.output}")
+    say(f"{done} frames -> {a.output}" + (f", {smooth.cuts_seen()} scene cuts" if smooth is not None else ""))
 
 
 if __name__ == "__main__":
