@@ -1,0 +1,186 @@
+"""Score an enhanced video stream on the HIP path, straight from its codec samples: per frame PSNR of Y / Cb / Cr and SSIM on luma against
+a ground-truth stream, mean luma, scene cuts and the brightness flicker of the stream (fdn_hip.video_metrics).  The evaluation side of
+inference_fdn_video.py: the same containers (raw or YUV4MPEG2) and sample layouts (yuv420p, nv12, yuv420p10le), opened by that driver's
+own reader, and no detour through 8-bit RGB, so 10 bit is scored as 10 bit.  No reference counterpart (the reference scores PNGs).
+
+    python calculate_video_metrics.py --ref gt.y4m enhanced.y4m --csv scores.csv
+    ffmpeg -i out.mp4 -f yuv4mpegpipe -strict -1 - | python calculate_video_metrics.py --ref gt.y4m -
+    python calculate_video_metrics.py --size 1280x720 --pix-fmt nv12 enhanced.yuv          # no ground truth: mean luma, cuts, flicker
+
+REF and DIST are paths, DIST may be `-` for stdin.  PSNR is on the codes (peak 2^bits - 1) whatever the range of the stream, the `average`
+pools the three planes as ffmpeg's psnr filter does; SSIM is the reference's _ssim_cly on the luma codes; mean_y and dmean (the change of
+mean luma against the frame before, `-` at a scene cut) are in 8-bit code units; flicker = mean |dmean| over the frames that are no cut.
+With --ref the cuts are found in REF.  stdout: one line per frame, `Average:` and `flicker:`; every message goes to stderr.  Streams of
+unequal length: the common prefix is scored, both lengths are named and the exit status is 1.  One process, one GPU; needs a ROCm GPU
+and the built libfdn_hip.so, there is no CPU fallback.
+"""
+import argparse
+import os
+import sys
+from types import SimpleNamespace
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from inference_fdn_video import SAMPLE_BYTES, open_video, say, size_arg, unit_fraction  # noqa: E402
+
+ME = "calculate_video_metrics.py"
+CSV_COLUMNS = ("frame", "psnr_y", "psnr_u", "psnr_v", "psnr_avg", "ssim_y", "mean_y_ref", "mean_y", "cut", "dmean_ref", "dmean")
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--ref", default=None, metavar="REF", help="ground-truth stream: a path (without it: mean luma, cuts and flicker only)")
+    ap.add_argument("dist", metavar="DIST", help="the stream to score: a path, or - for stdin")
+    ap.add_argument("--format", choices=("auto", "raw", "y4m"), default="auto",
+                    help="auto: YUV4MPEG2 when a stream starts with its magic, else raw (which needs --size)")
+    ap.add_argument("--size", type=size_arg, default=None, metavar="WxH", help="frame size of a raw stream")
+    ap.add_argument("--pix-fmt", choices=tuple(SAMPLE_BYTES), default=None, help="sample layout (default: the Y4M header's, yuv420p for raw)")
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--scene-cut", type=unit_fraction(False), default=0.3, metavar="FRACTION",
+                    help="a scene cut is where more than this fraction of the pixels changed their luma bin (of 256) against the frame "
+                         "before; 1 = never (default 0.3)")
+    ap.add_argument("--csv", default=None, metavar="PATH", help="write the per-frame records there, floats as repr() writes them")
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    if a.batch < 1:
+        ap.error("--batch must be at least 1")
+    if a.ref == "-":
+        ap.error("REF is a path: only DIST may be stdin")
+    return a
+
+
+DRIVER_PREFIX = "inference_fdn_video.py: "                              # what the driver's open_video puts before its one-line refusals
+
+
+def close_streams(*readers):
+    """close what open_stream opened (stdin is left alone)"""
+    for r in readers:
+        if r is not None and r.stream is not sys.stdin.buffer:
+            r.stream.close()
+
+
+def open_stream(a, path):
+    """-> (FrameReader, VideoFormat, width, height) of one stream through the video driver's open_video; SystemExit with one line"""
+    try:
+        src = sys.stdin.buffer if path == "-" else open(path, "rb")
+    except OSError as e:
+        raise SystemExit(f"{ME}: {path}: {e.strerror}")
+    try:
+        return open_video(SimpleNamespace(format=a.format, size=a.size, pix_fmt=a.pix_fmt, matrix="auto", range=None, chroma_loc=None), src)[:4]
+    except SystemExit as e:
+        if src is not sys.stdin.buffer:
+            src.close()
+        msg = str(e.code)
+        raise SystemExit(f"{ME}: {path}: {msg[len(DRIVER_PREFIX):] if msg.startswith(DRIVER_PREFIX) else msg}")
+
+
+def open_pair(a):
+    """both streams, checked against each other before anything touches the GPU -> (dist reader, ref reader or None, fmt, w, h)"""
+    dist, fmt, w, h = open_stream(a, a.dist)
+    ref = None
+    try:
+        if a.ref is not None:
+            ref, rfmt, rw, rh = open_stream(a, a.ref)
+            if (rw, rh) != (w, h):
+                raise SystemExit(f"{ME}: the streams differ in size: {a.ref} is {rw}x{rh}, {a.dist} is {w}x{h}")
+            if rfmt.pix_fmt != fmt.pix_fmt:
+                raise SystemExit(f"{ME}: the streams differ in pix_fmt: {a.ref} is {rfmt.pix_fmt}, {a.dist} is {fmt.pix_fmt}")
+    except SystemExit:
+        close_streams(dist, ref)
+        raise
+    return dist, ref, fmt, w, h
+
+
+def _num(v, spec):
+    return "-" if v is None else format(v, spec)
+
+
+def frame_line(i, r, has_ref):
+    if has_ref:
+        return (f"{i:6d}: PSNR y {r['psnr_y']:.4f} u {r['psnr_u']:.4f} v {r['psnr_v']:.4f} avg {r['psnr_avg']:.4f} dB, SSIM-Y {r['ssim_y']:.6f}, "
+                f"mean_y {r['mean_y']:.3f} (ref {r['mean_y_ref']:.3f}), cut {int(r['cut'])}, dmean {_num(r['dmean'], '+.4f')} "
+                f"(ref {_num(r['dmean_ref'], '+.4f')})")
+    return f"{i:6d}: mean_y {r['mean_y']:.3f}, cut {int(r['cut'])}, dmean {_num(r['dmean'], '+.4f')}"
+
+
+def csv_row(i, r):
+    def cell(k):
+        v = i if k == "frame" else r[k]
+        return "" if v is None else str(int(v)) if k in ("frame", "cut") else repr(float(v))
+    return ",".join(cell(k) for k in CSV_COLUMNS)
+
+
+def drain(reader, buf):
+    """frames left in a stream whose partner has ended (counted, not scored)"""
+    while reader.read_batch(buf) == buf.shape[0]:
+        pass
+    return reader.frames
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    dist, ref, fmt, w, h = open_pair(a)
+    try:
+        score_streams(a, dist, ref, fmt, w, h)
+    finally:
+        close_streams(dist, ref)
+
+
+def score_streams(a, dist, ref, fmt, w, h):
+    say(f"{w}x{h} {fmt.pix_fmt}" + (f", {a.dist} against {a.ref}" if ref is not None else f", {a.dist} on its own"))
+
+    import numpy as np
+    import torch
+    from fdn_hip.video_metrics import VideoScore
+    dev = torch.device(a.device)
+    torch.cuda.set_device(dev)
+    score = VideoScore(h, w, fmt, cut=a.scene_cut, device=dev)
+    n = fmt.frame_samples(h, w)
+    as_bytes = lambda t: t.numpy().view(np.uint8).reshape(a.batch, -1)  # noqa: E731
+    buf_d = torch.empty((a.batch, n), dtype=fmt.dtype)
+    buf_r = torch.empty((a.batch, n), dtype=fmt.dtype) if ref is not None else None
+    out = open(a.csv, "w") if a.csv else None
+    if out:
+        out.write(",".join(CSV_COLUMNS) + "\n")
+    done = 0
+    try:
+        while True:
+            nd = dist.read_batch(as_bytes(buf_d))
+            nr = ref.read_batch(as_bytes(buf_r)) if ref is not None else nd
+            k = min(nd, nr)
+            if k:
+                recs = score.update(buf_d[:k].to(dev), None if ref is None else buf_r[:k].to(dev))
+                for r in recs:
+                    print(frame_line(done, r, ref is not None))
+                    if out:
+                        out.write(csv_row(done, r) + "\n")
+                    done += 1
+            if nd < a.batch or nr < a.batch:
+                break
+        len_d = dist.frames if nd < a.batch else drain(dist, as_bytes(buf_d))
+        len_r = len_d if ref is None else (ref.frames if nr < a.batch else drain(ref, as_bytes(buf_r)))
+    finally:
+        if out:
+            out.close()
+    s = score.summary()
+    if done:
+        if ref is not None:
+            print(f"Average: PSNR y {s['psnr_y']:.4f} u {s['psnr_u']:.4f} v {s['psnr_v']:.4f} avg {s['psnr_avg']:.4f} dB (over the stream: y "
+                  f"{s['psnr_y_global']:.4f} avg {s['psnr_avg_global']:.4f} dB), SSIM-Y {s['ssim_y']:.6f}, mean_y {s['mean_y']:.3f} "
+                  f"(ref {s['mean_y_ref']:.3f}), {s['cuts']} scene cuts in {done} frames")
+        else:
+            print(f"Average: mean_y {s['mean_y']:.3f}, {s['cuts']} scene cuts in {done} frames")
+        if s["flicker"] == s["flicker"]:                                  # not nan: some frame followed a frame of its scene
+            print(f"flicker: {s['flicker']:.4f}" + (f" (ref {s['flicker_ref']:.4f}, against ref {s['flicker_err']:.4f})" if ref is not None else "")
+                  + " mean |dmean|, 8-bit code units")
+    sys.stdout.flush()
+    for rd, path in ((dist, a.dist), (ref, a.ref)):
+        if rd is not None and rd.error:                                   # a stream cut mid-frame, as the video driver words it
+            raise SystemExit(f"{ME}: {path}: {rd.error}; {done} frames scored")
+    if len_d != len_r:
+        raise SystemExit(f"{ME}: the streams differ in length: {a.ref} has {len_r} frames, {a.dist} has {len_d}; the first {done} were scored")
+    say(f"{done} frames scored" + (f" -> {a.csv}" if a.csv else ""))
+
+
+if __name__ == "__main__":
+    main()
