@@ -323,21 +323,30 @@ def calculate_niqe(img, crop_border=0, input_order="CHW", convert_to="y", params
 
 
 # ---- LPIPS (scripts/metrics/calculate_lpips.py: lpips.LPIPS(net='vgg'), version 0.1) --------------------------------------------------------
-_lpips_models = {}          # (net, weights path, lin path, device) -> LPIPS: the weights are loaded once per file and device
+_lpips_models = {}          # (net, weights path, lin path, device) -> (the files' (mtime, size), LPIPS): the weights are loaded once per file version and device
+
+
+def _file_stamp(path):
+    if path is None:
+        return None
+    st = os.stat(path)
+    return st.st_mtime_ns, st.st_size
 
 
 def lpips_model(net="vgg", weights=None, lin_weights=None, device=None):
-    """fdn_hip.lpips.LPIPS for these weights; built once per (net, files, device) when the weights are given as paths"""
+    """fdn_hip.lpips.LPIPS for these weights; built once per (net, files, device) when the weights are given as paths, and again when
+    a file has been rewritten in place (its modification time or size differs; the model of the old contents is dropped)"""
     from .lpips import LPIPS
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     paths = all(w is None or isinstance(w, (str, os.PathLike)) for w in (weights, lin_weights))
     if not paths:
         return LPIPS(net, weights, lin_weights, dev)
     key = (net, None if weights is None else os.path.abspath(weights), None if lin_weights is None else os.path.abspath(lin_weights), str(dev))
-    m = _lpips_models.get(key)
-    if m is None:
-        m = _lpips_models[key] = LPIPS(net, weights, lin_weights, dev)
-    return m
+    stamp = (_file_stamp(key[1]), _file_stamp(key[2]))
+    hit = _lpips_models.get(key)
+    if hit is None or hit[0] != stamp:
+        hit = _lpips_models[key] = (stamp, LPIPS(net, weights, lin_weights, dev))
+    return hit[1]
 
 
 def _u8_images(img, dev):

@@ -53,7 +53,13 @@ class WeightCache:
     """Derived weight tensors of ONE module (concatenated / folded / packed operands), rebuilt when a source
     parameter changes (data pointer or version).  Entries are stream-safe: the building stream records an event and
     any other stream that later hits the entry waits on it once, so a cold model may be driven from several HIP
-    streams at once (pipeline.forward_streams).  The cache lives on its module: it dies with it."""
+    streams at once (pipeline.forward_streams).  The cache lives on its module: it dies with it.
+
+    What it sees: an in-place update under no_grad (`p.mul_()`, `p.detach().copy_()`, load_state_dict), a replaced Parameter
+    (load_state_dict(assign=True), `m.weight = nn.Parameter(...)`), `p.data = new`, a source that appears or disappears.
+    What it cannot see: a write THROUGH `.data` (`p.data.mul_(3)`, `p.data.copy_(new)`, `m.weight.data *= scale`) changes the
+    values and leaves both the version counter and the pointer alone, so the derived operands (and pipeline.weights_signature,
+    hence the captured graphs) stay those of the old values.  After such a write call `forget_derived(model, ...)`."""
 
     def __init__(self):
         self._store = {}
@@ -74,10 +80,7 @@ class WeightCache:
                 ev = torch.cuda.Event()
                 ev.record(cur)
                 if hit is not None:                 # other streams may still be reading the operands being replaced
-                    for t in (hit[1] if isinstance(hit[1], (tuple, list)) else (hit[1],)):
-                        if torch.is_tensor(t) and t.is_cuda:
-                            for sid in hit[3]:
-                                t.record_stream(torch.cuda.ExternalStream(sid, device=t.device))
+                    self._retire(hit)
             hit = (key, val, ev, {cur.cuda_stream} if cuda else set(), tuple(srcs))
             self._store[name] = hit
         elif cuda and cur.cuda_stream not in hit[3]:
@@ -91,6 +94,42 @@ class WeightCache:
 
     def __deepcopy__(self, memo):          # HIP events do not copy; a copied module rebuilds its derived weights
         return WeightCache()
+
+    def __getstate__(self):                # pickle / torch.save(net): HIP events do not pickle either; no entry travels
+        return {"_store": {}}              # (not an empty state: the old pickle protocols skip __setstate__ for a false one)
+
+    def __setstate__(self, st):
+        self._store = {}
+
+    @staticmethod
+    def _retire(hit):
+        for t in (hit[1] if isinstance(hit[1], (tuple, list)) else (hit[1],)):
+            if torch.is_tensor(t) and t.is_cuda:
+                for sid in hit[3]:
+                    t.record_stream(torch.cuda.ExternalStream(sid, device=t.device))
+
+    def clear(self):
+        for hit in self._store.values():
+            self._retire(hit)
+        self._store = {}
+
+
+_forgotten = 0              # advanced by forget_derived; part of pipeline.weights_signature, so the graph holders capture again
+
+
+def forget_derived(*modules):
+    """Drop everything derived from the weights of these module trees: every WeightCache on them is emptied, the GraphedForward that
+    pipeline.run keeps on a model is dropped, and a process-wide counter that pipeline.weights_signature includes is advanced, so
+    GraphedForward / GraphedStep holders (of any model) capture again.  The way out after a write through `.data`, which neither a
+    version counter nor a pointer shows (see WeightCache)."""
+    global _forgotten
+    _forgotten += 1
+    for root in modules:
+        for m in root.modules():
+            m.__dict__.pop("_fdn_graphed", None)
+            for v in m.__dict__.values():
+                if isinstance(v, WeightCache):
+                    v.clear()
 
 
 def fold_ln(w, bias, gamma, beta):

@@ -93,13 +93,14 @@ def forward_streams(net, lpnet, x, n_streams=1, keep=None):
 def weights_signature(*modules):
     """What a captured graph depends on besides the input shape: the storage mode, the routing switches that decide WHICH kernels a
     forward launches (the matrix-pipe mode, the optional one-launch FDSA route), the CU budgets that decide their launch geometry
-    (fdn_hip.set_cu_budget) and every parameter / buffer of the live module trees (count, in-place version counters, addresses).  A
-    captured graph replays the kernels of its capture: after set_matrix_pipe() or a change of ops.FDSA_FULL the key differs and the
-    holder captures again."""
+    (fdn_hip.set_cu_budget) and every parameter / buffer of the live module trees: its (address, in-place version counter) pair, in
+    tree order - sums over the tree would not see two parameters that swap storages - plus the counter that ops.forget_derived
+    advances (a write through `.data` shows in neither the address nor the version).  A captured graph replays the kernels of its
+    capture: after set_matrix_pipe() or a change of ops.FDSA_FULL the key differs and the holder captures again."""
     from . import _cu_budgets, matrix_pipe_mode, ops
     ps = [p for m in modules for p in list(m.parameters()) + list(m.buffers())]
     return (storage_dtype(), matrix_pipe_mode(), tuple(sorted(_cu_budgets.items())), bool(ops.FDSA_FULL), int(ops.FDSA_FULL_MAX_C), bool(ops.FDSA_TAIL), bool(ops.FDSA_TAIL_PIN), int(ops.FDSA_TAIL_PIN_MAX_C), str(ops.FFN_TAIL_MODE), bool(ops.SPECTRAL_MLP_FUSED), bool(ops.GEMM_OWN_STATS), bool(ops.UPCONV_GATHER), bool(ops.AFF_MULTIRES),
-            len(ps), sum(p._version for p in ps), sum(p.data_ptr() & 0xFFFFFFFF for p in ps))
+            int(ops._forgotten), tuple((p.data_ptr(), p._version) for p in ps))
 
 
 class GraphedForward:

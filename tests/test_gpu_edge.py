@@ -318,6 +318,26 @@ def test_graphed_forward_bit_identical(A):
     check(4)
     net.net_p.output.weight = torch.nn.Parameter(net.net_p.output.weight.detach().clone() * 2.0)   # a replaced Parameter object
     check(5)
+    # parameters that feed WeightCache entries (the FDSA tail image, its pin variant, the concatenated gammas): the replay must not read operands
+    # derived from the old values, and neither may the eager forward it is compared with (a cold deep copy has no derived operands yet)
+    import copy
+    po, ln = net.net_p.encoder_level1[0].attn.project_out, net.net_p.encoder_level1[1].attn.norm1.body
+
+    def check_cold(seed):
+        x = dev(torch.rand(1, 3, 64, 96, generator=torch.Generator().manual_seed(seed)))
+        with torch.no_grad():
+            cold = copy.deepcopy(net)(x, ratio_i=lp(x))[0]
+        assert torch.equal(g(x), cold), seed
+
+    with torch.no_grad():
+        po.weight.mul_(1.5)                                     # in place
+        ln.weight.mul_(1.1)
+    check(30)
+    check_cold(31)
+    po.weight = torch.nn.Parameter(po.weight.detach().clone() * 0.8)      # replaced objects
+    ln.weight = torch.nn.Parameter(ln.weight.detach().clone() * 1.1)
+    check(32)
+    check_cold(33)
     try:
         fdn_hip.set_storage_dtype("bf16")                       # a graph recorded in fp32 storage must not be replayed in bf16 mode
         check(6)

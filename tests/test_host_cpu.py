@@ -382,6 +382,16 @@ def test_graph_key_covers_every_routing_switch():
     with torch.no_grad():
         m.weight.add_(1.0)                      # an in-place weight update is seen too
     assert pipeline.weights_signature(m) != base
+    # a graph holds raw pointers: two equal-shaped parameters that swap storages change what it reads and leave every sum over the tree alone
+    two = torch.nn.Sequential(torch.nn.Linear(3, 3), torch.nn.Linear(3, 3))
+    base2 = pipeline.weights_signature(two)
+    assert pipeline.weights_signature(two) == base2
+    two[0].weight.data, two[1].weight.data = two[1].weight.data, two[0].weight.data
+    assert pipeline.weights_signature(two) != base2, "swapped storages are not seen by the graph key"
+    two[0].weight.data, two[1].weight.data = two[1].weight.data, two[0].weight.data
+    assert pipeline.weights_signature(two) == base2
+    ops.forget_derived(two)                     # the way out after a write through .data moves the key as well
+    assert pipeline.weights_signature(two) != base2
 
 
 # ---- (ABI 17) the routes of the generic full-image FFT: fdn_fft_route is host arithmetic, the launchers decide by the same code ----
