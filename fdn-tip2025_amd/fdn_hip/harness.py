@@ -23,6 +23,10 @@ Video frames (no reference counterpart): preprocess_yuv420 / postprocess_yuv420 
 frames as a decoder hands them out (VideoFormat: yuv420p, nv12, yuv420p10le) and the same forward, through fdn_pre_yuv420 /
 fdn_post_yuv420 (include/fdn_video.h): codec samples -> fp32 -> codec samples, rounded once.  enhance_yuv420(temporal=RatioFilter) filters
 the ratio across the frames of a stream (fdn_hip.temporal, include/fdn_temporal.h).
+
+ensemble = 2, 4 or 8 (enhance_u8, validate_u8, enhance_frame_tiled; no reference counterpart) is the geometric self-ensemble of
+fdn_hip.ensemble: FDN runs on that many flipped / transposed copies of each frame - or, tiled, of each tile - with the ratio of the
+untransformed frame or tile, and the results, mapped back, are averaged.  ensemble = 1 is the code path without the keyword.
 """
 import ctypes
 from dataclasses import dataclass
@@ -189,7 +193,7 @@ def _forward(net, lpnet, x, ratio_mode, ratio):
 
 @torch.no_grad()
 def enhance_u8(net, lpnet, img_u8, bgr=True, ratio_mode="lolblur", ratio=None, tile=None, ratio_from="frame", overlap=0, batch=8,
-               blend="average"):
+               blend="average", ensemble=1):
     """uint8 in -> uint8 out through LPNet -> FDN (the body of the reference's per-image loop, batched).
     ratio_mode: "lolblur" feeds LPNet's prediction (inference_fdn_lolblur.py:69-71), "lolv1" feeds
     mean(gray)/prediction (inference_fdn_lolv1.py:57-62), "fixed" feeds the caller's `ratio` [B,1] and skips LPNet - the
@@ -197,11 +201,15 @@ def enhance_u8(net, lpnet, img_u8, bgr=True, ratio_mode="lolblur", ratio=None, t
     tile: None = every frame in one forward; (crop_h, crop_w), multiples of 32, or "auto" (tiling.auto_tile: only frames above
     tiling.WHOLE_FRAME_MAX_PIXELS) = frame by frame through enhance_frame_tiled, `batch` tiles per forward, neighbours sharing at least
     `overlap` pixels, the ratio taken from the whole frame or per tile (ratio_from, see tile_ratio; "fixed" then also takes [B,T,1]),
-    the tiles merged by the reference's average or feathered (blend, see tiling.merge).  Without a tile, blend does nothing."""
+    the tiles merged by the reference's average or feathered (blend, see tiling.merge).  Without a tile, blend does nothing.
+    ensemble: 1, 2, 4 or 8 copies of every frame (of every tile, with a tile) through FDN, averaged (fdn_hip.ensemble); the ratio is the
+    one the call without `ensemble` feeds, taken once from the untransformed frame, and the forwards are eager, `batch` samples each."""
+    from .ensemble import check_ensemble
     from .tiling import check_blend
     if ratio_mode not in ("lolblur", "lolv1", "fixed"):
         raise ValueError(f"ratio_mode {ratio_mode!r}")
     check_blend(blend)
+    check_ensemble(ensemble)
     if img_u8.dim() == 3:
         img_u8 = img_u8.unsqueeze(0)
     if tile is not None and img_u8.dim() == 4 and resolve_tile(tile, img_u8.shape[1], img_u8.shape[2]) is not None:
@@ -209,21 +217,40 @@ def enhance_u8(net, lpnet, img_u8, bgr=True, ratio_mode="lolblur", ratio=None, t
             raise FdnHipError(f"ratio_mode 'fixed' needs ratio [B,1] or [B,T,1] for B = {img_u8.shape[0]}")
         return torch.stack([enhance_frame_tiled(net, lpnet, img_u8[b], tile, bgr=bgr, ratio_mode=ratio_mode, ratio_from=ratio_from,
                                                 ratio=None if ratio is None else ratio[b].reshape(-1, 1), overlap=overlap, batch=batch,
-                                                blend=blend)[0]
+                                                blend=blend, ensemble=ensemble)[0]
                             for b in range(img_u8.shape[0])])
+    if ensemble != 1:
+        if ratio_mode == "fixed":
+            if ratio is None or tuple(ratio.shape) != (img_u8.shape[0], 1):
+                raise FdnHipError(f"ratio_mode 'fixed' needs ratio [B,1] for B = {img_u8.shape[0]}")
+        else:
+            ratio = frame_ratio(lpnet, preprocess(img_u8, bgr=bgr)[0], ratio_mode)
+        return _ensemble_u8(net, img_u8, ratio, ensemble, batch, img_u8.shape[1], img_u8.shape[2], bgr)
     x, h, w = preprocess(img_u8, bgr=bgr)
     return postprocess(_forward(net, lpnet, x, ratio_mode, ratio).contiguous(), h, w, bgr=bgr)
 
 
+def _ensemble_u8(net, img_u8, ratio, ensemble, batch, h, w, bgr):
+    """uint8 frames [B,h,w,3] + their ratio [B,1] -> uint8 [B,h,w,3] through the copies of fdn_hip.ensemble"""
+    from . import ensemble as ens
+    res_a, res_b, mask = ens.forward_ensemble(net, img_u8, ratio, ensemble, batch, bgr=bgr)
+    return ens.post_u8(res_a, res_b, mask, h, w, bgr=bgr)
+
+
 @torch.no_grad()
 def enhance_frame_tiled(net, lpnet, img_u8, tile, bgr=True, ratio_mode="lolblur", ratio_from="frame", ratio=None, gt_u8=None, overlap=0,
-                        batch=8, run=None, blend="average"):
+                        batch=8, run=None, blend="average", ensemble=1):
     """One uint8 frame [h,w,3] through the tiled route -> (uint8 [h,w,3], ratio [T,1]).  tile: (crop_h, crop_w) or "auto" (which must
     resolve to a tile here); ratio_mode / ratio_from / ratio / gt_u8 as tile_ratio takes them.  run(tiles, ratio) -> outs replaces
     tiling.run_tiles(net, tiles, ratio, batch) - the drivers pass the root's side of tiling.run_tiles_sharded.  blend: how the tiles are
-    merged, "average" or "feather" (tiling.merge_u8); the merge runs here, on the root, whoever ran the tiles."""
+    merged, "average" or "feather" (tiling.merge_u8); the merge runs here, on the root, whoever ran the tiles.  ensemble: copies of every
+    tile through FDN with the tile's ratio, averaged before the merge (tiling.run_tiles); not with a caller's `run`, whose ranks are set
+    up for one tile shape."""
     from . import tiling
+    from .ensemble import check_ensemble
     tiling.check_blend(blend)
+    if check_ensemble(ensemble) != 1 and run is not None:
+        raise ValueError("ensemble > 1 with a caller's run=: the sharded tile server takes one tile shape; run the ensemble on one GPU")
     if img_u8.dim() != 3 or img_u8.shape[-1] != 3:
         raise FdnHipError(f"expected one uint8 frame [h,w,3], got {tuple(img_u8.shape)}")
     h, w, _ = img_u8.shape
@@ -232,13 +259,13 @@ def enhance_frame_tiled(net, lpnet, img_u8, tile, bgr=True, ratio_mode="lolblur"
         raise FdnHipError(f"a {h}x{w} frame needs no tile: run it on the untiled path")
     tiles, ij = tiling.split_u8(img_u8, crop[0], crop[1], bgr=bgr, overlap=overlap)
     r = tile_ratio(lpnet, img_u8, tiles, ratio_mode, ratio_from, bgr=bgr, ratio=ratio, gt_u8=gt_u8, batch=batch)
-    outs = tiling.run_tiles(net, tiles, r, batch) if run is None else run(tiles, r)
+    outs = tiling.run_tiles(net, tiles, r, batch, ensemble=ensemble) if run is None else run(tiles, r)
     return tiling.merge_u8(outs, ij, h, w, bgr=bgr, blend=blend), r
 
 
 @torch.no_grad()
 def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=True, tile=None, ratio_from="frame", overlap=0, batch=8,
-                blend="average"):
+                blend="average", ensemble=1):
     """One validation step of the reference (image_restoration_model.py:578-586, :650-658, :746-748, :844-848) for a batch, on the device:
     uint8 low-quality and ground-truth frames [B,h,w,3] -> (uint8 result [B,h,w,3], PSNR list, SSIM list, ratio [B,1]).
     ratio_mode: "gt" feeds mean(gray(lq)) / mean(gray(gt)) as the validation does (gt_ratio; lpnet is not used and may be None),
@@ -246,12 +273,14 @@ def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=Tr
     (img1) against gt_u8, as the reference scores tensor2img's images (fdn_hip.metrics.calculate_psnr_ssim_u8).  Eager forward on the
     caller's stream.
     tile / ratio_from / overlap / batch / blend as in enhance_u8; ratio_from "tile" is the reference's val.grids validation.  With a tile
-    the returned ratio is [B,T,1], one row per tile."""
+    the returned ratio is [B,T,1], one row per tile.  ensemble as in enhance_u8: the same ratio, the averaged result scored."""
+    from .ensemble import check_ensemble
     from .metrics import calculate_psnr_ssim_u8
     from .tiling import check_blend
     if ratio_mode not in ("gt", "lolblur", "lolv1"):
         raise ValueError(f"ratio_mode {ratio_mode!r}")
     check_blend(blend)
+    check_ensemble(ensemble)
     if ratio_mode != "gt" and lpnet is None:
         raise FdnHipError(f"ratio_mode {ratio_mode!r} needs lpnet")
     if lq_u8.dim() == 3:
@@ -262,7 +291,7 @@ def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=Tr
         raise FdnHipError(f"Image shapes are different: {tuple(lq_u8.shape)}, {tuple(gt_u8.shape)}.")
     if tile is not None and lq_u8.dim() == 4 and resolve_tile(tile, lq_u8.shape[1], lq_u8.shape[2]) is not None:
         done = [enhance_frame_tiled(net, lpnet, lq_u8[b], tile, bgr=bgr, ratio_mode=ratio_mode, ratio_from=ratio_from, gt_u8=gt_u8[b],
-                                    overlap=overlap, batch=batch, blend=blend) for b in range(lq_u8.shape[0])]
+                                    overlap=overlap, batch=batch, blend=blend, ensemble=ensemble) for b in range(lq_u8.shape[0])]
         out = torch.stack([o for o, _ in done])
         psnr, ssim = calculate_psnr_ssim_u8(out, gt_u8, crop_border=crop_border, bgr=bgr)
         return out, psnr, ssim, torch.stack([r for _, r in done])
@@ -274,7 +303,10 @@ def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=Tr
     else:
         ratio = lolv1_ratio(x, lpnet(x))
     ratio = ratio.contiguous()
-    out = postprocess(net(x, ratio_i=ratio, device=x.device)[0].contiguous(), h, w, bgr=bgr)
+    if ensemble != 1:
+        out = _ensemble_u8(net, lq_u8, ratio, ensemble, batch, h, w, bgr)
+    else:
+        out = postprocess(net(x, ratio_i=ratio, device=x.device)[0].contiguous(), h, w, bgr=bgr)
     psnr, ssim = calculate_psnr_ssim_u8(out, gt_u8, crop_border=crop_border, bgr=bgr)
     return out, psnr, ssim, ratio
 

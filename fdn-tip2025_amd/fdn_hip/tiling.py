@@ -204,14 +204,22 @@ def merge_u8(outs, ij, h, w, bgr=True, blend="average"):
 
 
 @torch.no_grad()
-def run_tiles(net, tiles, ratio, batch=8):
-    """FDN on tiles (T,3,ch,cw) with ratio (T,1), `batch` tiles per forward (the last forward may take fewer) -> outs (T,3,ch,cw)."""
+def run_tiles(net, tiles, ratio, batch=8, ensemble=1):
+    """FDN on tiles (T,3,ch,cw) with ratio (T,1), `batch` tiles per forward (the last forward may take fewer) -> outs (T,3,ch,cw).
+    ensemble 2, 4 or 8: every tile goes through FDN in that many flipped / transposed copies with its own ratio, and outs holds their
+    average (fdn_hip.ensemble: fdn_d4_apply -> forwards -> fdn_d4_mean)."""
+    from .ensemble import check_ensemble
+    check_ensemble(ensemble)
     T = tiles.shape[0]
     if tuple(ratio.shape) != (T, 1):
         raise FdnHipError(f"run_tiles needs ratio [{T},1], got {tuple(ratio.shape)}")
     if batch < 1:
         raise FdnHipError(f"batch must be at least 1, got {batch}")
     ratio = ratio.to(device=tiles.device, dtype=torch.float32)
+    if ensemble != 1:
+        from . import ensemble as ens
+        res_a, res_b, mask = ens.forward_ensemble(net, tiles.contiguous(), ratio, ensemble, batch)
+        return ens.mean(res_a, res_b, mask, tiles.shape[2], tiles.shape[3])
     outs = torch.empty_like(tiles)
     for s in range(0, T, batch):
         t = tiles[s:s + batch]
@@ -256,18 +264,23 @@ def end_serving(dist, root=0):
 
 
 @torch.no_grad()
-def forward_tiled(net, lpnet, x, crop_h, crop_w, batch=8, ratio=None, overlap=0, blend="average"):
+def forward_tiled(net, lpnet, x, crop_h, crop_w, batch=8, ratio=None, overlap=0, blend="average", ensemble=1):
     """LPNet -> FDN on overlapping tiles of one padded image (crop sizes multiples of 32), merged like the reference.  ratio: [T,1]
     (one per tile) or [1,1] (one for the frame) feeds FDN instead of LPNet's per-tile prediction; overlap as tile_origins takes it,
-    blend as merge takes it."""
+    blend as merge takes it, ensemble as run_tiles takes it (LPNet's prediction is then taken from the untransformed tile)."""
+    from .ensemble import check_ensemble
     check_blend(blend)
+    check_ensemble(ensemble)
     if crop_h % 32 or crop_w % 32:
         raise FdnHipError("tile sizes must be multiples of 32 (three levels x 8x8 patches)")
     tiles, ij = split(x.contiguous(), crop_h, crop_w, overlap)
     if ratio is not None:
         if ratio.dim() != 2 or ratio.shape[1] != 1 or ratio.shape[0] not in (1, tiles.shape[0]):
             raise FdnHipError(f"ratio must be [1,1] or [{tiles.shape[0]},1], got {tuple(ratio.shape)}")
-        return merge(run_tiles(net, tiles, ratio.expand(tiles.shape[0], 1), batch), ij, x.shape[2], x.shape[3], blend)
+        return merge(run_tiles(net, tiles, ratio.expand(tiles.shape[0], 1), batch, ensemble), ij, x.shape[2], x.shape[3], blend)
+    if ensemble != 1:
+        ratio = torch.cat([lpnet(tiles[s:s + batch]) for s in range(0, tiles.shape[0], batch)])
+        return merge(run_tiles(net, tiles, ratio, batch, ensemble), ij, x.shape[2], x.shape[3], blend)
     outs = torch.empty_like(tiles)
     for s in range(0, tiles.shape[0], batch):
         t = tiles[s:s + batch]

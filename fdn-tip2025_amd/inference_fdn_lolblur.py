@@ -14,6 +14,10 @@ val.grids cuts them, each through FDN, averaged where they overlap (--tile-blend
 no step runs along the line where a tile ends; --tile-overlap sets the least width of those bands); the ratio comes from the whole frame
 (--tile-ratio frame) or from each tile (tile: the reference's semantics).  Under `python -m torch.distributed.run --nproc_per_node N`
 with --tile, rank 0 reads, splits, merges and writes, and the tiles of each frame are dealt to all N GPUs.
+
+--ensemble 2|4|8 is the geometric self-ensemble (fdn_hip.ensemble): every frame - or every tile - runs through FDN in that many flipped /
+transposed copies with the ratio of the untransformed frame, and the results, mapped back, are averaged: 2, 4 or 8 forwards per frame.
+One GPU only.  No accuracy gain has been measured with it here (no trained checkpoint at hand).
 """
 import argparse
 import glob
@@ -73,6 +77,14 @@ def add_tile_args(ap, ratio_default="frame"):
                         help=f"take the ratio from the whole frame or from each tile (default {ratio_default})")
 
 
+def add_ensemble_arg(ap):
+    """--ensemble: the number of flipped / transposed copies per frame, fdn_hip.ensemble.MASKS"""
+    ap.add_argument("--ensemble", type=int, choices=(1, 2, 4, 8), default=1,
+                    help="geometric self-ensemble: run FDN on this many flipped / transposed copies of every frame (or tile) and average "
+                         "the results mapped back: 2 = plus the column mirror, 4 = all mirrors, 8 = all mirrors and transpositions; "
+                         "default 1 (off)")
+
+
 _hinted = False
 
 
@@ -127,8 +139,11 @@ def run_driver(doc, build_models, ratio_mode="lolblur", fdn_keys="FDN checkpoint
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--device", default="cuda:0")
     add_tile_args(ap)
+    add_ensemble_arg(ap)
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world > 1 and a.ensemble > 1:
+        ap.error("--ensemble above 1 runs on one GPU only: the sharded tile server takes one tile shape")
     if world > 1 and a.tile is None:
         ap.error("WORLD_SIZE > 1 needs --tile: the ranks share the tiles of one frame; sharding whole frames by file is not supported")
 
@@ -165,7 +180,7 @@ def run_driver(doc, build_models, ratio_mode="lolblur", fdn_keys="FDN checkpoint
         hint_large_frame(a.tile, h, w)
         hint_hard_seam(a.tile, a.tile_blend, a.tile_overlap, h, w)
         if dist is None:
-            return enhance_u8(net, lp, batch, bgr=False, ratio_mode=ratio_mode, tile=a.tile, **tile_kw)
+            return enhance_u8(net, lp, batch, bgr=False, ratio_mode=ratio_mode, tile=a.tile, ensemble=a.ensemble, **tile_kw)
         if resolve_tile(a.tile, h, w) is None:
             return enhance_u8(net, lp, batch, bgr=False, ratio_mode=ratio_mode)
         return torch.stack([enhance_frame_tiled(net, lp, img, a.tile, bgr=False, ratio_mode=ratio_mode,

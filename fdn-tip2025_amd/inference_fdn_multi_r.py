@@ -6,7 +6,8 @@ repeated, ratio_i carries the grid, LPNet is not needed (its prediction only sup
     python inference_fdn_multi_r.py --fdn FDN_lolblur.pth --input frame.png --output multi_r/ [--start 0 --stop 1 --step 0.01]
 
 --tile HxW|auto runs a frame larger than one forward can take as overlapping tiles (fdn_hip.harness.enhance_u8), one grid value at a time;
---tile-blend feather merges them with ramps across their overlaps instead of the uniform average.
+--tile-blend feather merges them with ramps across their overlaps instead of the uniform average.  --ensemble 2|4|8 averages FDN's results
+on that many flipped / transposed copies of the frame (fdn_hip.ensemble), each fed the grid value.
 """
 import argparse
 import os
@@ -17,7 +18,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from inference_fdn_lolblur import add_tile_args, hint_hard_seam, hint_large_frame, load_params, read_rgb, write_rgb  # noqa: E402
+from inference_fdn_lolblur import add_ensemble_arg, add_tile_args, hint_hard_seam, hint_large_frame, load_params, read_rgb, write_rgb  # noqa: E402
 
 
 def sweep_values(start, stop, step):
@@ -41,6 +42,7 @@ def main():
     ap.add_argument("--batch", type=int, default=8, help="grid values per forward")
     ap.add_argument("--device", default="cuda:0")
     add_tile_args(ap, ratio_default=None)                     # the sweep's ratio is fixed: nothing to take from a frame or a tile
+    add_ensemble_arg(ap)
     a = ap.parse_args()
 
     from basicsr.models.archs.FDN_arch import FDN
@@ -58,7 +60,7 @@ def main():
         chunk = vals[c0:c0 + a.batch]
         ratio = torch.tensor(chunk, dtype=torch.float32, device=dev).view(-1, 1)
         out = enhance_u8(net, None, img.unsqueeze(0).expand(len(chunk), -1, -1, -1).contiguous(), bgr=False, ratio_mode="fixed", ratio=ratio,
-                         tile=a.tile, overlap=a.tile_overlap, batch=a.batch, blend=a.tile_blend)
+                         tile=a.tile, overlap=a.tile_overlap, batch=a.batch, blend=a.tile_blend, ensemble=a.ensemble)
         for v, o in zip(chunk, out.cpu().numpy()):
             write_rgb(os.path.join(a.output, output_name(v)), o)
     print(f"{len(vals)} ratios -> {a.output}")

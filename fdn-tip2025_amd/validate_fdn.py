@@ -14,7 +14,9 @@ scores take one small copy per batch.  Needs a ROCm GPU and the built libfdn_hip
 --tile HxW plays the reference's `val.grids` with crop_size_h / crop_size_w (:261-339, :737-743): every frame is cut into overlapping tiles,
 the ratio is taken per tile as the reference does after grids() (--tile-ratio tile, the default here; frame: one ratio from the whole
 frame), and the merged 8-bit frame is scored.  The csv then holds one ratio per tile, joined by ';'.  --tile-blend feather merges the
-tiles with ramps across their overlaps instead of the reference's average (not what the reference scores).
+tiles with ramps across their overlaps instead of the reference's average (not what the reference scores).  --ensemble 2|4|8 scores the
+geometric self-ensemble (fdn_hip.ensemble; not what the reference scores either): FDN on that many flipped / transposed copies of every
+frame or tile, all fed the ratio of the untransformed one, averaged.
 """
 import argparse
 import glob
@@ -61,8 +63,9 @@ def parse_args(argv=None):
     ap.add_argument("--csv", default=None, help="file for one 'frame,psnr,ssim,ratio' line per pair")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--device", default="cuda:0")
-    from inference_fdn_lolblur import add_tile_args
+    from inference_fdn_lolblur import add_ensemble_arg, add_tile_args
     add_tile_args(ap, ratio_default="tile")
+    add_ensemble_arg(ap)
     a = ap.parse_args(argv)
     if a.ratio == "lpnet" and not a.lpnet:
         ap.error("--ratio lpnet needs --lpnet")
@@ -106,7 +109,8 @@ def main(argv=None):
             hint_large_frame(a.tile, lqs.shape[1], lqs.shape[2])
             hint_hard_seam(a.tile, a.tile_blend, a.tile_overlap, lqs.shape[1], lqs.shape[2])
             out, p, s, r = validate_u8(net, lp, lq, gt, ratio_mode=mode, crop_border=a.crop_border, bgr=False, tile=a.tile,
-                                       ratio_from=a.tile_ratio, overlap=a.tile_overlap, batch=a.batch, blend=a.tile_blend)
+                                       ratio_from=a.tile_ratio, overlap=a.tile_overlap, batch=a.batch, blend=a.tile_blend,
+                                       ensemble=a.ensemble)
             r = r.reshape(r.shape[0], -1).cpu().tolist()              # one ratio per frame, or one per tile of a tiled frame
             frames = out.cpu().numpy() if a.dest else None
             for k, i in enumerate(idx):
