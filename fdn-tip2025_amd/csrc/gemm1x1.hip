@@ -23,11 +23,16 @@
 // MFMAs issue.  Prologues (LayerNorm, 3xLayerNorm * v_value, LayerNorm * x1 + x1) are applied in
 // registers between the load and the MFMA.
 #include "common.hpp"
+#include "conv1x1_route.hpp"
 #include <type_traits>
+
+// the launchers of gemm_tile.hip (FDN_CONV1X1_TILE) and gemm_split.hip (FDN_CONV1X1_SPLIT, FDN_CONV1X1_SPLIT_STRIP)
+int fdn_gemm_tile_launch(const conv1x1_route& r, const fdn_conv1x1_desc& d, hipStream_t s);
+int fdn_gemm_split_launch(const conv1x1_route& r, const fdn_conv1x1_desc& d, hipStream_t s);
 
 namespace {
 
-constexpr int KC = 32;     // K chunk (16 MFMA k-steps)
+using namespace c1x1;      // KC: the K chunk (16 MFMA k-steps)
 using f32x16 = fdn_f32x16;
 
 // The activation / epilogue kind are wave-uniform runtime values of the descriptor.  Tested per element they cost a chain
@@ -1167,326 +1172,191 @@ __global__ __launch_bounds__(256, 2) void conv1x1_kstream_vec_kernel(fdn_conv1x1
     }
 }
 
-int pick_mt(int N) {
-    // fewest computed 32-row tiles, then fewest passes; MT <= 5 keeps the accumulator at 80 VGPRs
-    const int tiles = (N + 31) / 32;
-    int best = 1, best_cost = 1 << 30;
-    for (int mt = 1; mt <= 5; ++mt) {
-        const int passes = (tiles + mt - 1) / mt;
-        const int cost = passes * mt * 100 + passes;
-        if (cost < best_cost || (cost == best_cost && mt > best)) { best_cost = cost; best = mt; }
-    }
-    return best;
-}
-
 // launch-time facts are cached per (kernel, device) in capi.hip (fdn_persistent_grid): no occupancy / attribute query on the hot path
 
+// The common tail of the persistent launchers: the route's threads per workgroup and pixels per tile, as many workgroups as `cap` lets be
+// co-resident (capped by the work)
+template <typename Kern>
+int launch_persistent(Kern kern, const conv1x1_route& r, const fdn_conv1x1_desc& d, hipStream_t s, Geo g, size_t lds, fdn_grid_cap cap) {
+    g.tiles_per_img = cdiv(d.P, r.tile_px);
+    g.total_tiles = d.B * g.tiles_per_img;
+    const int grid = fdn_persistent_grid(kern, r.threads, lds, g.total_tiles, cap);
+    if (grid < 0) return FDN_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(r.threads), lds, s, d, g);
+    return fdn_launch_status();
+}
+
 template <int MT, int PRO, int NW, bool EARLY>
-int launch(const fdn_conv1x1_desc& d, hipStream_t s) {
-    const int nch = PRO == FDN_PRO_LN3_GATE ? ((d.ln_group + 1) / 2 + 4) / 5 : (d.K + KC - 1) / KC;   // as in the kernel
+int launch(const conv1x1_route& r, const fdn_conv1x1_desc& d, hipStream_t s) {
+    const int nch = PRO == FDN_PRO_LN3_GATE ? ((d.ln_group + 1) / 2 + 4) / 5 : k_chunks(d.K);   // as in the kernel
     const size_t tab = 2UL * nch * KC * sizeof(float);
     const size_t chunk = (size_t)KC * (MT * 32 + 1) * sizeof(float);
-    Geo g;
+    Geo g = {};
     g.resident = (tab + nch * chunk <= 96 * 1024) ? 1 : 0;
     size_t lds = tab + (g.resident ? nch : 2) * chunk;
     g.bias_off = (int)(lds / sizeof(float));
     lds += (size_t)(((d.N + 31) & ~31) + 32 * 5) * sizeof(float);     // bias table (+ the rows a partial last pass still indexes)
-    g.tiles_per_img = cdiv(d.P, NW * 32);
-    g.total_tiles = d.B * g.tiles_per_img;
-    auto kern = conv1x1_kernel<MT, PRO, NW, EARLY>;
-    // persistent grid: as many workgroups as can be co-resident (LDS / register limited), capped by the work;
     // 16 waves per CU (4 per SIMD) are enough to hide the loads
-    const int grid = fdn_persistent_grid(kern, NW * 64, lds, g.total_tiles, {true, 0, 16, 0});
-    if (grid < 0) return FDN_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, s, d, g);
-    return fdn_launch_status();
+    return launch_persistent(conv1x1_kernel<MT, PRO, NW, EARLY>, r, d, s, g, lds, {true, 0, 16, 0});
 }
 
 template <int NCH, int PRO>
-int launch_smallk(const fdn_conv1x1_desc& d, hipStream_t s) {
-    const int ntiles = (d.N + 31) / 32;
-    const size_t lds = (2UL * NCH * KC + (size_t)NCH * KC * (ntiles * 32 + 1) + ntiles * 32) * sizeof(float);
-    constexpr int NW = 8;
-    Geo g;
+int launch_smallk(const conv1x1_route& r, const fdn_conv1x1_desc& d, hipStream_t s) {
+    Geo g = {};
     g.resident = 1;
-    g.tiles_per_img = cdiv(d.P, NW * 32);
-    g.total_tiles = d.B * g.tiles_per_img;
-    auto kern = conv1x1_smallk_kernel<NCH, PRO, NW>;
-    const int grid = fdn_persistent_grid(kern, NW * 64, lds, g.total_tiles, {false, 3, 0, 160 * 1024});
-    if (grid < 0) return FDN_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, s, d, g);
-    return fdn_launch_status();
+    return launch_persistent(conv1x1_smallk_kernel<NCH, PRO, 8>, r, d, s, g, smallk_lds(NCH, d.N), {false, 3, 0, 160 * 1024});
 }
 
 template <int NCH, int PRO>
-int launch_smallk_stream(const fdn_conv1x1_desc& d, hipStream_t s) {
-    constexpr int NW = 8;
-    const size_t lds = (2UL * NCH * KC + 2UL * NCH * KC * 33 + ((d.N + 31) / 32) * 32) * sizeof(float);
-    Geo g;
-    g.resident = 0;
-    g.tiles_per_img = cdiv(d.P, NW * 32);
-    g.total_tiles = d.B * g.tiles_per_img;
-    auto kern = conv1x1_smallk_stream_kernel<NCH, PRO, NW>;
-    const int grid = fdn_persistent_grid(kern, NW * 64, lds, g.total_tiles, {false, 1, 0, 0});   // 8 waves x ~190 VGPRs: one workgroup per CU
-    if (grid < 0) return FDN_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, s, d, g);
-    return fdn_launch_status();
+int launch_smallk_stream(const conv1x1_route& r, const fdn_conv1x1_desc& d, hipStream_t s) {
+    // 8 waves x ~190 VGPRs: one workgroup per CU
+    return launch_persistent(conv1x1_smallk_stream_kernel<NCH, PRO, 8>, r, d, s, Geo{}, smallk_stream_lds(NCH, d.N), {false, 1, 0, 0});
 }
 
 template <int NCH, int PRO, int VEC, bool TAIL = false, bool XBF = false, bool OBF = false>
-int launch_smallk_vec(const fdn_conv1x1_desc& d, hipStream_t s) {
-    const int ntiles = (d.N + 31) / 32;
-    const size_t lds = (2UL * NCH * KC + (size_t)NCH * KC * (ntiles * 32 + 1) + ntiles * 32) * sizeof(float);
-    Geo g;
+int launch_smallk_vec(const conv1x1_route& r, const fdn_conv1x1_desc& d, hipStream_t s) {
+    Geo g = {};
     g.resident = 1;
-    g.tiles_per_img = cdiv(d.P, 4 * 32 * VEC);
-    g.total_tiles = d.B * g.tiles_per_img;
-    auto kern = conv1x1_smallk_vec_kernel<NCH, PRO, VEC, TAIL, XBF, OBF>;
-    const int grid = fdn_persistent_grid(kern, 256, lds, g.total_tiles, {true, 4, 0, 0});
-    if (grid < 0) return FDN_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, d, g);
-    return fdn_launch_status();
-}
-
-// 8- / 16-byte lanes: P and the batch strides in whole 16-byte units, x, out and the operands the form reads or writes besides
-// (p2, p3: null = none) 16-byte aligned
-bool vec_aligned(const fdn_conv1x1_desc& d, const void* p2 = nullptr, const void* p3 = nullptr) {
-    if (d.P % 4 != 0 || d.xbs[0] % 4 != 0 || d.obs % 4 != 0) return false;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(d.x[0]) | reinterpret_cast<uintptr_t>(d.out) | reinterpret_cast<uintptr_t>(p2) | reinterpret_cast<uintptr_t>(p3);
-    return (a & 15) == 0;
-}
-// the vectorised project_out forms: residual or no epilogue operand, statistics allowed
-bool vec_out_ok(const fdn_conv1x1_desc& d) {
-    if (d.epi != FDN_EPI_NONE && d.epi != FDN_EPI_RES) return false;
-    if (d.epi == FDN_EPI_RES && d.rbs % 4 != 0) return false;
-    return vec_aligned(d, d.epi == FDN_EPI_RES ? d.res : nullptr, d.stats_out);
-}
-
-// the vectorised kernel covers: small-K shapes (see smallk_ok) with one segment, no epilogue operand, plain / LN prologue,
-// P a multiple of 4 and 16-byte aligned tensors
-bool smallk_vec_ok(const fdn_conv1x1_desc& d) {
-    if (d.kseg[1] > 0 || d.kseg[2] > 0 || d.epi != FDN_EPI_NONE || (d.pro != FDN_PRO_NONE && d.pro != FDN_PRO_LN)) return false;
-    return vec_aligned(d, d.pro != FDN_PRO_NONE ? d.stats : nullptr);
+    return launch_persistent(conv1x1_smallk_vec_kernel<NCH, PRO, VEC, TAIL, XBF, OBF>, r, d, s, g, smallk_lds(NCH, d.N), {true, 4, 0, 0});
 }
 
 template <int NCH, int PRO>
-int launch_smallk_stream_vec(const fdn_conv1x1_desc& d, hipStream_t s) {
-    const size_t lds = (2UL * NCH * KC + 2UL * NCH * KC * 33 + ((d.N + 31) / 32) * 32) * sizeof(float);
-    Geo g;
-    g.resident = 0;
-    g.tiles_per_img = cdiv(d.P, 8 * 32 * 2);
-    g.total_tiles = d.B * g.tiles_per_img;
-    auto kern = conv1x1_smallk_stream_vec_kernel<NCH, PRO>;
-    const int grid = fdn_persistent_grid(kern, 512, lds, g.total_tiles, {false, 1, 0, 0});
-    if (grid < 0) return FDN_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, d, g);
-    return fdn_launch_status();
+int launch_smallk_stream_vec(const conv1x1_route& r, const fdn_conv1x1_desc& d, hipStream_t s) {
+    return launch_persistent(conv1x1_smallk_stream_vec_kernel<NCH, PRO>, r, d, s, Geo{}, smallk_stream_lds(NCH, d.N), {false, 1, 0, 0});
 }
 
-template <int MT, bool XBF = false>
-int launch_kstream_vec(const fdn_conv1x1_desc& d, hipStream_t s) {
-    const int nch = (d.K + KC - 1) / KC;
+template <int MT, bool XBF>
+int launch_kstream_vec(const conv1x1_route& r, const fdn_conv1x1_desc& d, hipStream_t s) {
+    const int nch = k_chunks(d.K);
     const size_t chunk = (size_t)KC * (MT * 32 + 1) * sizeof(float);
-    Geo g;
+    Geo g = {};
     g.resident = (nch * chunk <= 64 * 1024) ? 1 : 0;
     size_t lds = (g.resident ? nch : 2) * chunk;
     g.bias_off = (int)(lds / sizeof(float));
     lds += (size_t)MT * 32 * sizeof(float);
-    g.tiles_per_img = cdiv(d.P, 4 * 32 * 2);
-    g.total_tiles = d.B * g.tiles_per_img;
-    auto kern = conv1x1_kstream_vec_kernel<MT, XBF>;
-    const int grid = fdn_persistent_grid(kern, 256, lds, g.total_tiles, {true, 4, 0, 0});
-    if (grid < 0) return FDN_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, d, g);
-    return fdn_launch_status();
+    return launch_persistent(conv1x1_kstream_vec_kernel<MT, XBF>, r, d, s, g, lds, {true, 4, 0, 0});
 }
 
-// plain deep-K convs for the 8-byte-lane K-streaming kernel
-bool kstream_vec_ok(const fdn_conv1x1_desc& d) {
-    if (d.pro != FDN_PRO_NONE || d.kseg[1] > 0 || d.kseg[2] > 0 || d.K <= 96 || d.N > 96) return false;   // (N = 128 spills: slower)
-    return vec_out_ok(d);                          // measured: 172 -> 64 at level 2 10.2 -> 7.0 ms (71 TFLOP/s)
-}
-
-// K <= 128, N >= 2K, single input segment, plain/LN prologue, no muladd epilogue, weights too big for LDS
-bool smallk_stream_ok(const fdn_conv1x1_desc& d) {
-    if (d.K > 128 || d.K <= 64 || d.stats_out || d.kseg[1] > 0) return false;
-    if (d.pro != FDN_PRO_NONE && d.pro != FDN_PRO_LN) return false;
-    if (d.epi == FDN_EPI_MULADD) return false;
-    return d.N >= 2 * d.K;
-}
-
-// narrow project_out convs for the vectorised kernel's TAIL form: K <= 96, N <= 32, no prologue, residual or no
-// epilogue operand, statistics allowed
-bool narrow_vec_ok(const fdn_conv1x1_desc& d) {
-    if (d.K > 96 || d.N > 32 || d.pro != FDN_PRO_NONE || d.kseg[1] > 0 || d.kseg[2] > 0) return false;
-    return vec_out_ok(d);
-}
-
-// true when the small-K kernel covers this problem
-bool smallk_ok(const fdn_conv1x1_desc& d) {
-    if (d.K > 64 || d.stats_out || d.pro == FDN_PRO_LN3_GATE) return false;
-    if (d.N < 2 * d.K || d.N < 64) return false;                  // made for N >> K
-    const int nch = (d.K + KC - 1) / KC, ntiles = (d.N + 31) / 32;
-    const size_t lds = (2UL * nch * KC + (size_t)nch * KC * (ntiles * 32 + 1)) * sizeof(float);
-    return lds <= 100 * 1024;
-}
-
-// The three pixel-pair ladders of fdn_conv1x1, for fp32 and for bf16 storage of the one operand the form allows (XBF: input, OBF: output).
-template <bool XBF>
-int launch_kstream_by_tiles(const fdn_conv1x1_desc& d, hipStream_t s) {
-    const int tiles = (d.N + 31) / 32;
-    if (tiles == 1) return launch_kstream_vec<1, XBF>(d, s);
-    if (tiles == 2) return launch_kstream_vec<2, XBF>(d, s);
-    return launch_kstream_vec<3, XBF>(d, s);
-}
-template <bool XBF>
-int launch_narrow_by_chunks(const fdn_conv1x1_desc& d, hipStream_t s) {
-    if (d.K <= KC) return launch_smallk_vec<1, FDN_PRO_NONE, 2, true, XBF, false>(d, s);
-    if (d.K <= 2 * KC) return launch_smallk_vec<2, FDN_PRO_NONE, 2, true, XBF, false>(d, s);
-    return launch_smallk_vec<3, FDN_PRO_NONE, 2, true, XBF, false>(d, s);
-}
-// measured (tools/bench_kernels.py to_hidden ffn_in, B=8 720p): 8-byte lanes win for K <= 32 (32->152: 1.65 -> 1.44 ms,
-// 32->86: 0.92 -> 0.76 ms) and for K <= 64 while the weight matrix leaves room for 3 workgroups per CU (64->172:
-// 0.74 -> 0.59 ms; 64->304 is slower vectorised: FDN_ERR_UNSUPPORTED = not taken); 16-byte lanes spill with the LN prologue
-template <bool OBF>
-int launch_smallk_vec_by_chunks(const fdn_conv1x1_desc& d, hipStream_t s) {
-    const int ntiles = (d.N + 31) / 32;
-    if (d.K <= KC) {
-        if (d.pro == FDN_PRO_LN) return launch_smallk_vec<1, FDN_PRO_LN, 2, false, false, OBF>(d, s);       // (16-byte lanes measure the same here)
-        return launch_smallk_vec<1, FDN_PRO_NONE, 2, false, false, OBF>(d, s);       // (8-byte lanes only: the kernel static_asserts VEC == 2)
-    }
-    if ((2UL * 2 * KC + 2UL * KC * (ntiles * 32 + 1)) * sizeof(float) <= 52 * 1024) {
-        if (d.pro == FDN_PRO_LN) return launch_smallk_vec<2, FDN_PRO_LN, 2, false, false, OBF>(d, s);
-        return launch_smallk_vec<2, FDN_PRO_NONE, 2, false, false, OBF>(d, s);
-    }
-    return FDN_ERR_UNSUPPORTED;
-}
-
-template <int PRO>
-int launch_smallk_nch(const fdn_conv1x1_desc& d, hipStream_t s) {
-    const int nch = (d.K + KC - 1) / KC;
-    if (nch == 1) return launch_smallk<1, PRO>(d, s);
-    return launch_smallk<2, PRO>(d, s);
-}
-
+// (form, parameters) -> instantiation.  A combination route_conv1x1 cannot produce is FDN_ERR_LAUNCH, never a silent default.
 template <int MT, int PRO>
-int launch_early(const fdn_conv1x1_desc& d, hipStream_t s) {
-    // narrow, shallow problems with an epilogue operand are load-latency bound: 4-wave workgroups (finer
-    // register granularity per CU) that fetch the epilogue operands ahead of the MFMAs
-    if constexpr (MT <= 2) {
-        if (d.epi != FDN_EPI_NONE && d.K <= 64) return launch<MT, PRO, 4, true>(d, s);
+int launch_generic(const conv1x1_route& r, const fdn_conv1x1_desc& d, hipStream_t s) {
+    if constexpr (MT <= 2 && PRO != FDN_PRO_LN3_GATE) {
+        if (r.early) return r.nw == 4 ? launch<MT, PRO, 4, true>(r, d, s) : FDN_ERR_LAUNCH;
     }
-    // measured (tools/gpu_gemm_shapes.py): 64-wide plain GEMMs (FDFFN project_out at level 2, 172 -> 64) gain from
-    // 4-wave workgroups at 3 waves per SIMD (13.5 -> 10.9 ms); wider tiles spill at that register budget
-    if constexpr (MT == 2 && PRO == FDN_PRO_NONE) return launch<MT, PRO, 4, false>(d, s);
-    // wide tiles: two independent 4-wave workgroups per CU instead of one of 8 - their per-chunk barriers drift apart,
-    // so one workgroup's MFMAs fill the other's load-issue / barrier phase (345 -> 128: 12.1 -> 11.3 ms)
-    if constexpr (MT >= 3 && PRO != FDN_PRO_LN_MULADD) return launch<MT, PRO, 4, false>(d, s);     // (LN_MULADD spills at that budget)
-    return launch<MT, PRO, 8, false>(d, s);
+    if (r.early) return FDN_ERR_LAUNCH;
+    if constexpr (generic_nw4(MT, PRO)) {
+        if (r.nw == 4) return launch<MT, PRO, 4, false>(r, d, s);
+    }
+    // (the 8-wave copy exists for every (MT, PRO), also where the route always answers 4: the object keeps the set of kernels it had)
+    if (r.nw == 8) return generic_nw4(MT, PRO) ? FDN_ERR_LAUNCH : launch<MT, PRO, 8, false>(r, d, s);
+    return FDN_ERR_LAUNCH;
+}
+template <int MT>
+int launch_generic_pro(const conv1x1_route& r, const fdn_conv1x1_desc& d, hipStream_t s) {
+    switch (r.pro) {
+        case FDN_PRO_NONE: return launch_generic<MT, FDN_PRO_NONE>(r, d, s);
+        case FDN_PRO_LN: return launch_generic<MT, FDN_PRO_LN>(r, d, s);
+        case FDN_PRO_LN3_GATE: return launch_generic<MT, FDN_PRO_LN3_GATE>(r, d, s);
+        case FDN_PRO_LN_MULADD: return launch_generic<MT, FDN_PRO_LN_MULADD>(r, d, s);
+    }
+    return FDN_ERR_LAUNCH;
 }
 
-template <int MT>
-int launch_pro(const fdn_conv1x1_desc& d, hipStream_t s) {
-    switch (d.pro) {
-        case FDN_PRO_NONE: return launch_early<MT, FDN_PRO_NONE>(d, s);
-        case FDN_PRO_LN: return launch_early<MT, FDN_PRO_LN>(d, s);
-        case FDN_PRO_LN3_GATE:
-            if constexpr (MT >= 2) return launch<MT, FDN_PRO_LN3_GATE, 4, false>(d, s);
-            return launch<MT, FDN_PRO_LN3_GATE, 8, false>(d, s);
-        case FDN_PRO_LN_MULADD: return launch_early<MT, FDN_PRO_LN_MULADD>(d, s);
-        default: return FDN_ERR_ARG;
+// NCH x {NONE, LN} of a launcher template: L<NCH, PRO>(r, d, s)
+#define FDN_BY_NCH_PRO(L, NCH)                                                             \
+    case NCH:                                                                              \
+        if (r.pro == FDN_PRO_NONE) return L<NCH, FDN_PRO_NONE>(r, d, s);                      \
+        if (r.pro == FDN_PRO_LN) return L<NCH, FDN_PRO_LN>(r, d, s);                          \
+        break
+
+template <bool XBF>
+int launch_kstream_by_tiles(const conv1x1_route& r, const fdn_conv1x1_desc& d, hipStream_t s) {
+    switch (r.n) {
+        case 1: return launch_kstream_vec<1, XBF>(r, d, s);
+        case 2: return launch_kstream_vec<2, XBF>(r, d, s);
+        case 3: return launch_kstream_vec<3, XBF>(r, d, s);
     }
+    return FDN_ERR_LAUNCH;
 }
+template <bool XBF>
+int launch_narrow_by_chunks(const conv1x1_route& r, const fdn_conv1x1_desc& d, hipStream_t s) {
+    switch (r.n) {
+        case 1: return launch_smallk_vec<1, FDN_PRO_NONE, 2, true, XBF, false>(r, d, s);
+        case 2: return launch_smallk_vec<2, FDN_PRO_NONE, 2, true, XBF, false>(r, d, s);
+        case 3: return launch_smallk_vec<3, FDN_PRO_NONE, 2, true, XBF, false>(r, d, s);
+    }
+    return FDN_ERR_LAUNCH;
+}
+template <int NCH, int PRO>
+int launch_smallk_vec_obf(const conv1x1_route& r, const fdn_conv1x1_desc& d, hipStream_t s) {
+    return r.obf ? launch_smallk_vec<NCH, PRO, 2, false, false, true>(r, d, s) : launch_smallk_vec<NCH, PRO, 2, false, false, false>(r, d, s);
+}
+
+int launch_route(const conv1x1_route& r, const fdn_conv1x1_desc& d, hipStream_t s) {
+    if (r.form != FDN_CONV1X1_GENERIC && (r.nw || r.early)) return FDN_ERR_LAUNCH;
+    if ((r.xbf && r.form != FDN_CONV1X1_KSTREAM_VEC && r.form != FDN_CONV1X1_NARROW_TAIL) || (r.obf && r.form != FDN_CONV1X1_SMALLK_VEC)) return FDN_ERR_LAUNCH;
+    switch (r.form) {
+        case FDN_CONV1X1_SPLIT:
+        case FDN_CONV1X1_SPLIT_STRIP: return fdn_gemm_split_launch(r, d, s);
+        case FDN_CONV1X1_TILE: return fdn_gemm_tile_launch(r, d, s);
+        case FDN_CONV1X1_SMALLK_STREAM_VEC:
+            switch (r.n) {
+                FDN_BY_NCH_PRO(launch_smallk_stream_vec, 2);
+                FDN_BY_NCH_PRO(launch_smallk_stream_vec, 3);
+                FDN_BY_NCH_PRO(launch_smallk_stream_vec, 4);
+            }
+            break;
+        case FDN_CONV1X1_SMALLK_STREAM:
+            switch (r.n) {
+                FDN_BY_NCH_PRO(launch_smallk_stream, 3);
+                FDN_BY_NCH_PRO(launch_smallk_stream, 4);
+            }
+            break;
+        case FDN_CONV1X1_KSTREAM_VEC: return r.xbf ? launch_kstream_by_tiles<true>(r, d, s) : launch_kstream_by_tiles<false>(r, d, s);
+        case FDN_CONV1X1_NARROW_TAIL: return r.xbf ? launch_narrow_by_chunks<true>(r, d, s) : launch_narrow_by_chunks<false>(r, d, s);
+        case FDN_CONV1X1_SMALLK_VEC:
+            if (r.n == 1 && r.pro == FDN_PRO_NONE) return launch_smallk_vec_obf<1, FDN_PRO_NONE>(r, d, s);
+            if (r.n == 1 && r.pro == FDN_PRO_LN) return launch_smallk_vec_obf<1, FDN_PRO_LN>(r, d, s);
+            if (r.n == 2 && r.pro == FDN_PRO_NONE) return launch_smallk_vec_obf<2, FDN_PRO_NONE>(r, d, s);
+            if (r.n == 2 && r.pro == FDN_PRO_LN) return launch_smallk_vec_obf<2, FDN_PRO_LN>(r, d, s);
+            break;
+        case FDN_CONV1X1_SMALLK:
+            switch (r.n) {
+                FDN_BY_NCH_PRO(launch_smallk, 1);
+                FDN_BY_NCH_PRO(launch_smallk, 2);
+            }
+            if (r.pro == FDN_PRO_LN_MULADD && r.n == 1) return launch_smallk<1, FDN_PRO_LN_MULADD>(r, d, s);
+            if (r.pro == FDN_PRO_LN_MULADD && r.n == 2) return launch_smallk<2, FDN_PRO_LN_MULADD>(r, d, s);
+            break;
+        case FDN_CONV1X1_GENERIC:
+            switch (r.n) {
+                case 1: return launch_generic_pro<1>(r, d, s);
+                case 2: return launch_generic_pro<2>(r, d, s);
+                case 3: return launch_generic_pro<3>(r, d, s);
+                case 4: return launch_generic_pro<4>(r, d, s);
+                case 5: return launch_generic_pro<5>(r, d, s);
+            }
+            break;
+    }
+    return FDN_ERR_LAUNCH;
+}
+#undef FDN_BY_NCH_PRO
 
 }  // namespace
-
-// gemm_tile.hip: LDS-tiled kernel for the deep N = 128 shapes; FDN_ERR_UNSUPPORTED = not one of them
-int fdn_gemm_tile(const fdn_conv1x1_desc& d, hipStream_t s);
-// gemm_split.hip: the same shapes and the N > 128 ones on the bf16 matrix pipe (split operands), when the caller supplies packed weights
-int fdn_gemm_split(const fdn_conv1x1_desc& d, hipStream_t s);
 
 extern "C" int fdn_conv1x1(const fdn_conv1x1_desc* dp, fdn_stream_t stream) {
     FDN_CHECK_ARG(dp != nullptr);
     fdn_conv1x1_desc d = *dp;
-    FDN_CHECK_ARG(d.B > 0 && d.K > 0 && d.N > 0 && d.P > 0);
-    FDN_CHECK_ARG(d.x[0] && d.w && d.out);
-    FDN_CHECK_ARG(d.kseg[0] + d.kseg[1] + d.kseg[2] == d.K);
-    FDN_CHECK_ARG(d.kseg[1] == 0 || d.x[1]);
-    FDN_CHECK_ARG(d.kseg[2] == 0 || d.x[2]);
-    // stats == NULL with a LayerNorm prologue: the K-streaming split-bf16 kernel takes the statistics itself (LN3_GATE / LN_MULADD with packed
-    // weights on a deep shape); every other kernel wants them from fdn_chan_stats or a producer's epilogue
-    const bool own_stats = d.pro != FDN_PRO_NONE && !d.stats;
-    if (own_stats) FDN_CHECK_ARG(d.pro == FDN_PRO_LN3_GATE || d.pro == FDN_PRO_LN_MULADD);
-    if (d.pro >= FDN_PRO_LN3_GATE) FDN_CHECK_ARG(d.gamma && d.beta);
-    if (d.pro == FDN_PRO_LN3_GATE) FDN_CHECK_ARG(d.xb && d.ln_group * 3 == d.K && d.kseg[0] == d.K);
-    if (d.pro == FDN_PRO_LN_MULADD) FDN_CHECK_ARG(d.xb);
-    if (d.epi == FDN_EPI_RES) FDN_CHECK_ARG(d.res);
-    if (d.epi == FDN_EPI_MULADD) FDN_CHECK_ARG(d.mul && d.add);
-    if (d.stats_out) FDN_CHECK_ARG(d.N <= 160);
     d.vec4 = 0;
-    // 32-bit buffer offsets: every per-image plane set must stay below 4 GiB (incl. the padded K / N tails)
-    {
-        const unsigned long long lim = 0xFFFFFFFFull, P4 = 4ull * d.P;
-        if ((unsigned long long)(d.K + 40) * P4 > lim || (unsigned long long)(d.N + 200) * P4 > lim) return FDN_ERR_UNSUPPORTED;
-        if (d.kseg[1] > 0 && ((d.kseg[0] & 1) || (d.kseg[1] & 1))) return FDN_ERR_UNSUPPORTED;   // k-step pairs must not straddle segments
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // bf16 STORAGE of one operand (the block-internal FDFFN tensors of levels 1-2): the pixel-pair kernels only -
-    //   x_bf16  : the project_out convs (narrow TAIL form / K-streaming form), fp32 result;
-    //   out_bf16: the project_in convs (small-K form, plain or LayerNorm prologue), fp32 input.
-    if (d.x_bf16 || d.out_bf16) {
-        if ((d.x_bf16 && d.out_bf16) || own_stats) return FDN_ERR_UNSUPPORTED;
-        if (d.x_bf16) {
-            if (kstream_vec_ok(d)) return launch_kstream_by_tiles<true>(d, s);
-            if (narrow_vec_ok(d)) return launch_narrow_by_chunks<true>(d, s);
-            return FDN_ERR_UNSUPPORTED;
-        }
-        if (smallk_ok(d) && smallk_vec_ok(d)) return launch_smallk_vec_by_chunks<true>(d, s);
-        return FDN_ERR_UNSUPPORTED;
-    }
-    {
-        const int rc = fdn_gemm_split(d, s);            // level 3 with packed weights: fp32 on the bf16 matrix pipe (gemm_split.hip)
-        if (rc != FDN_ERR_UNSUPPORTED) return rc;
-    }
-    if (own_stats) return FDN_ERR_UNSUPPORTED;
-    {
-        const int rc = fdn_gemm_tile(d, s);             // 459 -> 128 (LN3 * v_value), 345 -> 128, 128 -> 128 at level 3
-        if (rc != FDN_ERR_UNSUPPORTED) return rc;
-    }
-    // K = 64 with a weight matrix too big to sit in LDS three times per CU (level-2 to_hidden, 64 -> 304): stream the weights too
-    if (d.K > KC && d.K <= 2 * KC && d.N >= 256 && !d.stats_out && d.kseg[1] == 0 && d.epi == FDN_EPI_NONE &&
-        (d.pro == FDN_PRO_NONE || d.pro == FDN_PRO_LN) && smallk_vec_ok(d)) {               // 15.1 -> 12.4 ms
-        if (d.pro == FDN_PRO_LN) return launch_smallk_stream_vec<2, FDN_PRO_LN>(d, s);
-        return launch_smallk_stream_vec<2, FDN_PRO_NONE>(d, s);
-    }
-    if (smallk_stream_ok(d) && d.epi == FDN_EPI_NONE && smallk_vec_ok(d)) {           // 128->612: 21.3 -> 20.0 ms, 128->345: 13.1 -> 10.9 ms
-        const int nch = (d.K + KC - 1) / KC;
-        if (d.pro == FDN_PRO_LN) return nch == 3 ? launch_smallk_stream_vec<3, FDN_PRO_LN>(d, s) : launch_smallk_stream_vec<4, FDN_PRO_LN>(d, s);
-        return nch == 3 ? launch_smallk_stream_vec<3, FDN_PRO_NONE>(d, s) : launch_smallk_stream_vec<4, FDN_PRO_NONE>(d, s);
-    }
-    if (smallk_stream_ok(d)) {
-        const int nch = (d.K + KC - 1) / KC;
-        if (d.pro == FDN_PRO_LN) return nch == 3 ? launch_smallk_stream<3, FDN_PRO_LN>(d, s) : launch_smallk_stream<4, FDN_PRO_LN>(d, s);
-        return nch == 3 ? launch_smallk_stream<3, FDN_PRO_NONE>(d, s) : launch_smallk_stream<4, FDN_PRO_NONE>(d, s);
-    }
-    if (kstream_vec_ok(d)) return launch_kstream_by_tiles<false>(d, s);
-    if (narrow_vec_ok(d)) return launch_narrow_by_chunks<false>(d, s);
-    if (smallk_ok(d) && smallk_vec_ok(d)) {
-        const int rc = launch_smallk_vec_by_chunks<false>(d, s);
-        if (rc != FDN_ERR_UNSUPPORTED) return rc;                  // (K > 32 with a wide weight matrix: the dword form below)
-    }
-    if (smallk_ok(d)) {
-        switch (d.pro) {
-            case FDN_PRO_NONE: return launch_smallk_nch<FDN_PRO_NONE>(d, s);
-            case FDN_PRO_LN: return launch_smallk_nch<FDN_PRO_LN>(d, s);
-            default: return launch_smallk_nch<FDN_PRO_LN_MULADD>(d, s);
-        }
-    }
-    switch (pick_mt(d.N)) {
-        case 1: return launch_pro<1>(d, s);
-        case 2: return launch_pro<2>(d, s);
-        case 3: return launch_pro<3>(d, s);
-        case 4: return launch_pro<4>(d, s);
-        default: return launch_pro<5>(d, s);
-    }
+    const conv1x1_route r = route_conv1x1(d, fdn_matrix_pipe_f32());
+    if (r.status != FDN_OK) return r.status;
+    return launch_route(r, d, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int fdn_conv1x1_route(const fdn_conv1x1_desc* dp, int* desc, int ndesc) {
+    FDN_CHECK_ARG(dp && desc && ndesc >= FDN_CONV1X1_ROUTE_DESC);
+    const conv1x1_route r = route_conv1x1(*dp, fdn_matrix_pipe_f32());
+    const int v[FDN_CONV1X1_ROUTE_DESC] = {r.status, r.form, r.n, r.pro, r.nw, r.early, r.xbf, r.obf, r.strip2, r.own_stats, r.bf16_pipe, r.threads, r.tile_px};
+    for (int i = 0; i < FDN_CONV1X1_ROUTE_DESC; ++i) desc[i] = v[i];
+    return FDN_OK;
 }

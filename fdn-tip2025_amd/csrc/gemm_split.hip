@@ -17,19 +17,17 @@
 // The weights are split once, off line, by fdn_conv1x1_pack into the same order, so staging them is a 16-byte copy.  Waves form a
 // 2 x 2 grid (two pixel strips x two channel tiles each): 24 MFMAs per k-step per wave behind 12 operand reads.
 #include "common.hpp"
+#include "conv1x1_route.hpp"
 
 namespace {
 
+using namespace c1x1;                         // TP, TN, KC, BLK, STRIP_MAX_N, TRI_E
 using f32x16 = fdn_f32x16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ f32x16 mf(fdn_u32x4 a, fdn_u32x4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
-constexpr int TP = 128, TN = 128, KC = 32;
-constexpr int BLK = 3 * 2 * 2 * 128;          // 16-byte units of one operand chunk: [part][k-step][lane half][row]
-constexpr int STRIP_MAX_N = 1024;             // widest output of the strip kernel (its bias lives in LDS)
-constexpr int TRI_E = 10;                     // LN3_GATE: channels e per chunk (10 triples = 30 k + 2 zero columns)
 
 struct SArgs {
     fdn_conv1x1_desc d;
@@ -672,20 +670,20 @@ __global__ __launch_bounds__(256, 2) void gemm_split_strip2_kernel(SArgs a, unsi
 }
 
 template <int NKS, int PRO>
-int launch_strip(const fdn_conv1x1_desc& d, hipStream_t s) {
+int launch_strip(const conv1x1_route& r, const fdn_conv1x1_desc& d, hipStream_t s) {
     SArgs a = {};
     a.d = d;
     a.tiles_per_img = cdiv(d.P, TP);
     a.total_ptiles = d.B * a.tiles_per_img;
     a.ntiles = 1;
-    if constexpr ((3 * NKS * 2 * 32) % 256 == 0 && NKS >= 6) {
-        const long wbytes = (long)cdiv(d.N, TN) * ((d.K + KC - 1) / KC) * BLK * 16;      // = fdn_conv1x1_pack_bytes(N, K, 0)
-        if (wbytes < 0x7FFFFFFFL) {
+    if constexpr (strip2_nks(NKS)) {
+        if (r.strip2) {
             fdn_note_bf16_launch();
-            hipLaunchKernelGGL((gemm_split_strip2_kernel<NKS, PRO>), dim3((unsigned)a.total_ptiles), dim3(256), 0, s, a, (unsigned)wbytes);
+            hipLaunchKernelGGL((gemm_split_strip2_kernel<NKS, PRO>), dim3((unsigned)a.total_ptiles), dim3(256), 0, s, a, (unsigned)split_pack_bytes(d.N, d.K, 0));
             return fdn_launch_status();
         }
     }
+    if (r.strip2) return FDN_ERR_LAUNCH;
     fdn_note_bf16_launch();
     hipLaunchKernelGGL((gemm_split_strip_kernel<NKS, PRO>), dim3((unsigned)a.total_ptiles), dim3(256), 0, s, a);
     return fdn_launch_status();
@@ -746,40 +744,33 @@ __global__ void pack_split_kernel(const float* __restrict__ w, fdn_u32x4* __rest
 
 }  // namespace
 
-// FDN_ERR_UNSUPPORTED = not a shape of this kernel (fdn_conv1x1 then picks another)
-int fdn_gemm_split(const fdn_conv1x1_desc& d, hipStream_t s) {
-    if (fdn_matrix_pipe_f32()) return FDN_ERR_UNSUPPORTED;
-    // lanes past the pixel count are masked with a byte offset of 2^31: it must stay outside every descriptor of this kernel
-    if ((unsigned long long)(d.N > d.K ? d.N : d.K) * 4ull * (unsigned long long)d.P > 0x7FFFFFFFull) return FDN_ERR_UNSUPPORTED;
-    if (!d.wpk || d.kseg[2] > 0 || d.act != FDN_ACT_NONE || d.x_bf16 || d.out_bf16) return FDN_ERR_UNSUPPORTED;
-    const bool two = d.kseg[1] > 0;                       // two inputs: the K-streaming kernel only, plain prologue, whole chunks per input
-    if (two && (d.pro != FDN_PRO_NONE || d.kseg[0] % KC != 0 || d.K < 96 || d.N < 96)) return FDN_ERR_UNSUPPORTED;
-    if ((long)d.B * cdiv(d.P, TP) * cdiv(d.N, TN) > 0x7FFFFFFFL) return FDN_ERR_UNSUPPORTED;
-    // short K, wide N, no epilogue: the activation strip stays in registers and the weights stream
-    const bool strip = !two && d.N <= STRIP_MAX_N && d.epi == FDN_EPI_NONE && !d.stats_out && (d.pro == FDN_PRO_NONE || d.pro == FDN_PRO_LN);
-    // (round 3) the project_in convs of levels 1-2 as well (32 -> 86, 64 -> 172; FDN_lolv1 24 -> 64, 48 -> 129): on the fp32 MFMA they kept
-    // the vector ALU's datapath 60-90 % busy (64 -> 172: 0.49 -> 0.41 ms, 32 -> 86: 0.82 -> 0.75 ms here)
-    if (strip && d.K > 16 && d.K <= 64 && 2 * d.N >= 5 * d.K) {
-        const bool ln = d.pro == FDN_PRO_LN;
-        if (d.K > 48) return ln ? launch_strip<4, FDN_PRO_LN>(d, s) : launch_strip<4, FDN_PRO_NONE>(d, s);
-        if (d.K > 32) return ln ? launch_strip<3, FDN_PRO_LN>(d, s) : launch_strip<3, FDN_PRO_NONE>(d, s);
-        return ln ? launch_strip<2, FDN_PRO_LN>(d, s) : launch_strip<2, FDN_PRO_NONE>(d, s);
+// route_conv1x1 decides (conv1x1_route.hpp: split_route); this only maps the route to its instantiation
+#define FDN_STRIP_CASE(NKS)                                                                   \
+    case NKS:                                                                                 \
+        if (r.pro == FDN_PRO_NONE) return launch_strip<NKS, FDN_PRO_NONE>(r, d, s);           \
+        if (r.pro == FDN_PRO_LN) return launch_strip<NKS, FDN_PRO_LN>(r, d, s);               \
+        break
+int fdn_gemm_split_launch(const conv1x1_route& r, const fdn_conv1x1_desc& d, hipStream_t s) {
+    if (r.form == FDN_CONV1X1_SPLIT_STRIP) {
+        switch (r.n) {
+            FDN_STRIP_CASE(2);
+            FDN_STRIP_CASE(3);
+            FDN_STRIP_CASE(4);
+            FDN_STRIP_CASE(6);
+            FDN_STRIP_CASE(7);
+            FDN_STRIP_CASE(8);
+        }
+    } else if (r.form == FDN_CONV1X1_SPLIT && !r.strip2) {
+        switch (r.pro) {
+            case FDN_PRO_NONE: return launch_split<FDN_PRO_NONE>(d, s);
+            case FDN_PRO_LN: return launch_split<FDN_PRO_LN>(d, s);
+            case FDN_PRO_LN3_GATE: return launch_split<FDN_PRO_LN3_GATE>(d, s);
+            case FDN_PRO_LN_MULADD: return launch_split<FDN_PRO_LN_MULADD>(d, s);
+        }
     }
-    if (d.K < 96 || d.N < 96 || (d.stats_out && d.N > TN)) return FDN_ERR_UNSUPPORTED;
-    if (d.K <= 128 && d.N >= 256 && strip) {
-        const bool ln = d.pro == FDN_PRO_LN;
-        if (d.K > 112) return ln ? launch_strip<8, FDN_PRO_LN>(d, s) : launch_strip<8, FDN_PRO_NONE>(d, s);
-        if (d.K > 96) return ln ? launch_strip<7, FDN_PRO_LN>(d, s) : launch_strip<7, FDN_PRO_NONE>(d, s);
-        return ln ? launch_strip<6, FDN_PRO_LN>(d, s) : launch_strip<6, FDN_PRO_NONE>(d, s);          // K = 96 (FDN_lolv1)
-    }
-    switch (d.pro) {
-        case FDN_PRO_NONE: return launch_split<FDN_PRO_NONE>(d, s);
-        case FDN_PRO_LN: return launch_split<FDN_PRO_LN>(d, s);
-        case FDN_PRO_LN3_GATE: return launch_split<FDN_PRO_LN3_GATE>(d, s);
-        case FDN_PRO_LN_MULADD: return launch_split<FDN_PRO_LN_MULADD>(d, s);
-    }
-    return FDN_ERR_UNSUPPORTED;
+    return FDN_ERR_LAUNCH;
 }
+#undef FDN_STRIP_CASE
 
 extern "C" long fdn_conv1x1_pack_bytes(int N, int K, int ln3_E);
 extern "C" long fdn_fcaffn_in_pack_bytes(int C) {
@@ -829,10 +820,7 @@ extern "C" int fdn_fcaffn_in_packed(const float* xi, const float* stats_xi, cons
     return fdn_launch_status();
 }
 
-extern "C" long fdn_conv1x1_pack_bytes(int N, int K, int ln3_E) {
-    const long nch = ln3_E > 0 ? (ln3_E + TRI_E - 1) / TRI_E : (K + KC - 1) / KC;
-    return (long)cdiv(N, TN) * nch * BLK * 16;
-}
+extern "C" long fdn_conv1x1_pack_bytes(int N, int K, int ln3_E) { return split_pack_bytes(N, K, ln3_E); }
 
 extern "C" int fdn_conv1x1_pack(const float* w, int N, int K, int ln3_E, void* wpk, fdn_stream_t stream) {
     FDN_CHECK_ARG(w && wpk && N > 0 && K > 0 && (ln3_E == 0 || 3 * ln3_E == K));

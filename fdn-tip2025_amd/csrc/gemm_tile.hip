@@ -9,12 +9,13 @@
 // while the chunk is staged.  The next chunk's global loads are in flight during the MFMAs of the current one; LDS is single
 // buffered (41 KB: three workgroups per CU cover each other's two barriers per chunk).
 #include "common.hpp"
+#include "conv1x1_route.hpp"
 
 namespace {
 
+using namespace c1x1;                       // TP, TN, KC
 using f32x16 = fdn_f32x16;
 
-constexpr int TP = 128, TN = 128, KC = 32;
 constexpr int LS = 161;                     // LDS row stride (floats): the two k of an MFMA step sit 33 banks apart, transposing weight writes hit 32 banks
 
 struct TArgs {
@@ -220,12 +221,9 @@ int launch_tile(const fdn_conv1x1_desc& d, hipStream_t s) {
 
 }  // namespace
 
-// FDN_ERR_UNSUPPORTED = not a shape of this kernel (fdn_conv1x1 then picks one of gemm1x1.hip's)
-int fdn_gemm_tile(const fdn_conv1x1_desc& d, hipStream_t s) {
-    if (d.N > TN || d.N < 96 || d.K < 96 || d.kseg[1] > 0 || d.kseg[2] > 0 || d.act != FDN_ACT_NONE || d.x_bf16 || d.out_bf16) return FDN_ERR_UNSUPPORTED;
-    if (d.epi != FDN_EPI_NONE && d.epi != FDN_EPI_RES) return FDN_ERR_UNSUPPORTED;
-    if ((long)d.B * cdiv(d.P, TP) > 0x7FFFFFFFL) return FDN_ERR_UNSUPPORTED;
-    if (d.pro == FDN_PRO_NONE) return launch_tile<FDN_PRO_NONE>(d, s);
-    if (d.pro == FDN_PRO_LN3_GATE) return launch_tile<FDN_PRO_LN3_GATE>(d, s);
-    return FDN_ERR_UNSUPPORTED;
+// route_conv1x1 decides (conv1x1_route.hpp: tile_route); this only maps the route to its instantiation
+int fdn_gemm_tile_launch(const conv1x1_route& r, const fdn_conv1x1_desc& d, hipStream_t s) {
+    if (r.form == FDN_CONV1X1_TILE && r.pro == FDN_PRO_NONE) return launch_tile<FDN_PRO_NONE>(d, s);
+    if (r.form == FDN_CONV1X1_TILE && r.pro == FDN_PRO_LN3_GATE) return launch_tile<FDN_PRO_LN3_GATE>(d, s);
+    return FDN_ERR_LAUNCH;
 }

@@ -38,7 +38,7 @@ class FdnHipError(RuntimeError):
     pass
 
 
-ABI_VERSION = 21        # include/fdn_hip.h: bumped on any signature change
+ABI_VERSION = 22        # include/fdn_hip.h: bumped on any signature change
 VIDEO_ABI_VERSION = 1   # include/fdn_video.h (the video frame entry points), likewise
 TEMPORAL_ABI_VERSION = 1  # include/fdn_temporal.h (the ratio filter across frames), likewise
 VMETRICS_ABI_VERSION = 1  # include/fdn_vmetrics.h (video evaluation from codec samples), likewise
@@ -82,8 +82,9 @@ def lib():
     return _lib
 
 
-def _declare(l):
-    """argtypes / restype of every entry point (a wrong argument count or kind raises here instead of corrupting the call)."""
+def _declare(l, missing_ok=False):
+    """argtypes / restype of every entry point (a wrong argument count or kind raises here instead of corrupting the call).
+    missing_ok: skip the entry points `l` lacks (tools/ab_libs.py loads builds of an older ABI beside this one)."""
     from ._abi import PROTOTYPES
     from ._abi_video import PROTOTYPES as VIDEO_PROTOTYPES
     from ._abi_temporal import PROTOTYPES as TEMPORAL_PROTOTYPES
@@ -92,7 +93,9 @@ def _declare(l):
     kinds = {"P": ctypes.c_void_p, "I": ctypes.c_int, "L": ctypes.c_long, "F": ctypes.c_float, "DESC": ctypes.POINTER(Conv1x1Desc)}
     tables = (PROTOTYPES, VIDEO_PROTOTYPES, TEMPORAL_PROTOTYPES, VMETRICS_PROTOTYPES, ENSEMBLE_PROTOTYPES)
     for name, (ret, sig) in [item for t in tables for item in t.items()]:
-        f = getattr(l, name)                       # AttributeError: the library lacks a symbol the header declares
+        f = getattr(l, name, None) if missing_ok else getattr(l, name)      # AttributeError: the library lacks a symbol the header declares
+        if f is None:
+            continue
         f.restype = ctypes.c_char_p if ret == "S" else ctypes.c_long if ret == "L" else ctypes.c_int
         f.argtypes = [kinds[k] for k in sig]
 

@@ -153,8 +153,25 @@ def conv1x1_pack(w, ln3_E=0):
     return wpk
 
 
+CONV1X1_FORMS = ("refused", "split", "split_strip", "tile", "smallk_stream_vec", "smallk_stream", "kstream_vec", "narrow_tail", "smallk_vec",
+                 "smallk", "generic")        # FDN_CONV1X1_* of include/fdn_hip.h, in order
+_ROUTE_FIELDS = ("status", "form", "n", "pro", "nw", "early", "xbf", "obf", "strip2", "own_stats", "bf16_pipe", "threads", "tile_px")
+
+
+def conv1x1_route(d):
+    """The kernel fdn_conv1x1 runs for the descriptor `d` (fdn_conv1x1_route; host arithmetic on its integers and pointer values, no GPU
+    needed): a dict of form (a name of CONV1X1_FORMS), n (the form's MT / NKS / NCH), pro, nw, early, xbf, obf, strip2, own_stats (the kernel
+    takes the LayerNorm statistics itself when d.stats is null), bf16_pipe, threads, tile_px and status (0, or the error fdn_conv1x1
+    would return: a refusal is an answer, not an exception)."""
+    desc = (ctypes.c_int * len(_ROUTE_FIELDS))()
+    check(lib().fdn_conv1x1_route(ctypes.byref(d), desc, len(desc)), "fdn_conv1x1_route")
+    rt = dict(zip(_ROUTE_FIELDS, desc))
+    rt["form"] = CONV1X1_FORMS[rt["form"]]
+    return rt
+
+
 def conv1x1(xs, w, bias=None, *, out=None, act=ACT_NONE, ln=None, ln3_gate=None, ln_muladd=None, res=None,
-            muladd=None, want_stats=False, cache=None, out_dtype=torch.float32):
+            muladd=None, want_stats=False, cache=None, out_dtype=torch.float32, route_only=False):
     """1x1 conv with fused prologue/epilogue (fdn_conv1x1).
 
     want_stats: also produce the channel-LayerNorm statistics of the output in the epilogue and attach
@@ -166,10 +183,12 @@ def conv1x1(xs, w, bias=None, *, out=None, act=ACT_NONE, ln=None, ln3_gate=None,
     its pixel tile; for every other shape the fdn_chan_stats launch happens here)
     res: residual added after act | muladd=(mul, add).
     cache=(WeightCache, name): where the derived operands are kept - the LayerNorm-folded weights of `ln` (else they are rebuilt
-    per call) and, for the deep shapes (K, N >= 96: level 3), the packed split-bf16 weights that put the GEMM on the bf16
-    matrix pipe (without a cache those shapes run the fp32-MFMA kernels).
+    per call) and, for the shapes the library has a split-bf16 kernel for (fdn_conv1x1_route says which: the deep level-3 shapes
+    and the wide project_in convs), the packed weights that put the GEMM on the bf16 matrix pipe (without a cache those shapes run
+    the fp32-MFMA kernels).
     out_dtype=torch.bfloat16 stores the result as bf16 (FDFFN project_in); a bf16 `xs` is read as bf16 storage
     (FDFFN project_out).  The library refuses forms it has no bf16 kernel for.
+    route_only=True: nothing is launched; returns the route (conv1x1_route) of the launch this call would make.
     """
     if torch.is_tensor(xs):
         xs = [xs]
@@ -208,11 +227,6 @@ def conv1x1(xs, w, bias=None, *, out=None, act=ACT_NONE, ln=None, ln3_gate=None,
         d.pro = PRO_LN_MULADD
         d.stats, d.gamma, d.beta = _flat(ln_muladd[0], "stats"), _flat(ln_muladd[1], "gamma"), _flat(ln_muladd[2], "beta")
         d.xb, d.xbbs = _planes(ln_muladd[3], "x1")
-    if (cache is not None and ((K >= 96 and N >= 96) or (16 < K <= 64 and 2 * N >= 5 * K and res is None and muladd is None and not want_stats)) and (len(xs) == 1 or (len(xs) == 2 and K >= 96 and N >= 96 and xs[0].shape[1] % 32 == 0 and d.pro == PRO_NONE)) and act == ACT_NONE and xs[0].dtype == torch.float32
-            and out.dtype == torch.float32):
-        srcs = [w0, bias0] + (list(ln[1:3]) if ln is not None else [])
-        d.wpk = ctypes.c_void_p(cache[0].get(cache[1] + ":pk", srcs, lambda w=w: conv1x1_pack(
-            w, K // 3 if ln3_gate is not None else 0)).data_ptr())
     d.act = act
     d.epi = EPI_NONE
     if res is not None:
@@ -223,22 +237,31 @@ def conv1x1(xs, w, bias=None, *, out=None, act=ACT_NONE, ln=None, ln3_gate=None,
         d.mul, d.mbs = _planes(muladd[0], "mul")
         d.add, mbs2 = _planes(muladd[1], "add")
         assert mbs2 == d.mbs
-    if d.pro in (PRO_LN3_GATE, PRO_LN_MULADD) and not d.stats and not d.wpk:
-        # only the K-streaming split-bf16 kernel (packed operands: the predicate above, bf16 matrix pipe) takes its tile's LayerNorm statistics itself;
-        # every other shape / mode gets the fdn_chan_stats launch here instead of a refused call first
-        auto = chan_stats(xs[0], groups=3) if ln3_gate is not None else chan_stats(xs[0])
-        d.stats = _flat(auto, "stats")
     stats = None
     if want_stats and N <= 160:
         stats = torch.empty((B, 1, 2, P), device=out.device, dtype=torch.float32)
         d.stats_out = _flat(stats, "stats_out")
-    rc = lib().fdn_conv1x1(ctypes.byref(d), stream())
-    if rc == ERR_UNSUPPORTED and d.pro in (PRO_LN3_GATE, PRO_LN_MULADD) and not d.stats:      # safety net: no kernel of this shape takes the statistics itself
-        x0 = xs[0]
-        auto = chan_stats(x0, groups=3) if ln3_gate is not None else chan_stats(x0)
+    # with a cache: the library says which kernel this descriptor reaches if packed weights come with it (a placeholder stands for them: never
+    # dereferenced); they are packed only for the split-bf16 forms, and only those take their tile's LayerNorm statistics themselves (own_stats)
+    rt, own_stats = None, False
+    if cache is not None:
+        d.wpk = ctypes.c_void_p(16)
+        rt = conv1x1_route(d)
+        d.wpk = None
+        if rt["form"] in ("split", "split_strip"):
+            srcs = [w0, bias0] + (list(ln[1:3]) if ln is not None else [])
+            d.wpk = ctypes.c_void_p(cache[0].get(cache[1] + ":pk", srcs, lambda w=w: conv1x1_pack(
+                w, K // 3 if ln3_gate is not None else 0)).data_ptr())
+            own_stats = rt["own_stats"]
+    need_stats = d.pro in (PRO_LN3_GATE, PRO_LN_MULADD) and not d.stats and not own_stats
+    if route_only:
+        if need_stats:
+            d.stats = ctypes.c_void_p(16)        # stands for the fdn_chan_stats result
+        return rt if d.wpk else conv1x1_route(d)
+    if need_stats:
+        auto = chan_stats(xs[0], groups=3) if ln3_gate is not None else chan_stats(xs[0])
         d.stats = _flat(auto, "stats")
-        rc = lib().fdn_conv1x1(ctypes.byref(d), stream())
-    check(rc, "fdn_conv1x1")
+    check(lib().fdn_conv1x1(ctypes.byref(d), stream()), "fdn_conv1x1")
     if want_stats:
         out._fdn_stats = stats if stats is not None else chan_stats(out)   # LayerNorm statistics travel with the tensor
     return out

@@ -72,7 +72,7 @@ int fdn_set_cu_budget(int cus);
  * LN_MULADD (LN(x)*xb + xb, gamma / beta [K]).
  * stats: [B][G][2][P] = (mean, rstd) from fdn_chan_stats, G = 3 for LN3_GATE else 1.  ABI 13: NULL with LN3_GATE / LN_MULADD = the kernel
  * takes the statistics of its pixel tile itself - only the K-streaming split-bf16 kernel does (packed weights, K and N >= 96); every
- * other shape returns FDN_ERR_UNSUPPORTED and wants the fdn_chan_stats launch.
+ * other shape returns FDN_ERR_UNSUPPORTED and wants the fdn_chan_stats launch (fdn_conv1x1_route: own_stats).
  * epi: NONE | RES (+res) | MULADD (*mul + add).  act is applied before epi. */
 typedef struct fdn_conv1x1_desc {
     const float* x[3];
@@ -105,6 +105,27 @@ typedef struct fdn_conv1x1_desc {
                          kernel; every other shape ignores it.  `w` must still be given. */
 } fdn_conv1x1_desc;
 int fdn_conv1x1(const fdn_conv1x1_desc* d, fdn_stream_t stream);
+
+/* (ABI 22) Which kernel fdn_conv1x1 runs for a descriptor: host arithmetic on the descriptor's integers and pointer values (null-ness and
+ * alignment; nothing is dereferenced, no GPU is needed) and the process's matrix-pipe mode - the code fdn_conv1x1 itself decides by
+ * (csrc/conv1x1_route.hpp).  (No reference counterpart.)  desc[0 .. FDN_CONV1X1_ROUTE_DESC) is filled with
+ *   [0] status: what fdn_conv1x1 would return before launching - FDN_OK, FDN_ERR_ARG or FDN_ERR_UNSUPPORTED (a refusal is an answer: the
+ *       call itself returns FDN_OK, and [1 ..] are 0)
+ *   [1] form, one per launcher: FDN_CONV1X1_SPLIT gemm_split_kernel<PRO> | _SPLIT_STRIP gemm_split_strip(2)_kernel<NKS, PRO> (both on the bf16
+ *       matrix pipe, packed weights) | _TILE gemm_tile_kernel<PRO> | _SMALLK_STREAM_VEC conv1x1_smallk_stream_vec_kernel<NCH, PRO> |
+ *       _SMALLK_STREAM conv1x1_smallk_stream_kernel<NCH, PRO> | _KSTREAM_VEC conv1x1_kstream_vec_kernel<MT, XBF> | _NARROW_TAIL
+ *       conv1x1_smallk_vec_kernel<NCH, NONE, 2, TAIL, XBF> | _SMALLK_VEC conv1x1_smallk_vec_kernel<NCH, PRO, 2, ., ., OBF> | _SMALLK
+ *       conv1x1_smallk_kernel<NCH, PRO> | _GENERIC conv1x1_kernel<MT, PRO, NW, EARLY>
+ *   [2] the form's MT / NKS / NCH (0: none)   [3] PRO of the instantiation   [4] NW   [5] EARLY (GENERIC only)   [6] XBF   [7] OBF
+ *   [8] SPLIT_STRIP: the direct-to-LDS kernel (strip2)
+ *   [9] own_stats: the kernel takes the LayerNorm statistics itself when d->stats is NULL   [10] the launch counts in fdn_bf16_mfma_launches
+ *   [11] threads per workgroup   [12] pixels per tile
+ * d or desc NULL, ndesc < FDN_CONV1X1_ROUTE_DESC: FDN_ERR_ARG. */
+enum { FDN_CONV1X1_REFUSED = 0, FDN_CONV1X1_SPLIT = 1, FDN_CONV1X1_SPLIT_STRIP = 2, FDN_CONV1X1_TILE = 3, FDN_CONV1X1_SMALLK_STREAM_VEC = 4,
+       FDN_CONV1X1_SMALLK_STREAM = 5, FDN_CONV1X1_KSTREAM_VEC = 6, FDN_CONV1X1_NARROW_TAIL = 7, FDN_CONV1X1_SMALLK_VEC = 8,
+       FDN_CONV1X1_SMALLK = 9, FDN_CONV1X1_GENERIC = 10 };
+enum { FDN_CONV1X1_ROUTE_DESC = 13 };
+int fdn_conv1x1_route(const fdn_conv1x1_desc* d, int* desc, int ndesc);
 
 /* Weights of a 1x1 conv split for the bf16 matrix pipe (gemm_split.hip): every fp32 weight is cut EXACTLY into three bf16 parts
  * (w = w1 + w2 + w3 by truncation) and laid out in MFMA operand order per (128-channel tile, 32-deep K chunk).  The kernel splits

@@ -100,9 +100,9 @@ def test_version_and_prototype_table(lib):
     assert _abi_ensemble.PROTOTYPES["fdn_d4_mean"] == ("I", ["P", "P", "P"] + ["I"] * 8 + ["P"])
     assert _abi_ensemble.PROTOTYPES["fdn_d4_post_u8"] == ("I", ["P", "P", "P"] + ["I"] * 9 + ["P"])
     tables = [_abi.PROTOTYPES, _abi_video.PROTOTYPES, _abi_temporal.PROTOTYPES, _abi_vmetrics.PROTOTYPES, _abi_ensemble.PROTOTYPES]
-    assert [len(t) for t in tables] == [73, 3, 3, 4, 5]
+    assert [len(t) for t in tables] == [74, 3, 3, 4, 5]
     assert len(set().union(*tables)) == sum(len(t) for t in tables)
-    assert fdn_hip.ABI_VERSION == lib.fdn_abi_version() == 21
+    assert fdn_hip.ABI_VERSION == lib.fdn_abi_version() == 22
     assert lib.fdn_d4_mean.argtypes == [ctypes.c_void_p] * 3 + [ctypes.c_int] * 8 + [ctypes.c_void_p]
     build_sh = open(os.path.join(ROOT, "fdn-tip2025_amd", "build.sh")).read()
     assert "../include/fdn_ensemble.h" in [ln for ln in build_sh.splitlines() if ln.startswith("NEWEST_HDR=")][0]

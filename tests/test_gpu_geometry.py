@@ -13,7 +13,8 @@ the channel-group clamps.  Each case is held to the float64 bound the suite alre
 the same bits as the device's count: no kernel here splits a reduction across workgroups, so which workgroup ran a pixel or a channel
 must not show in it.
 
-Persistent kernels: tiles per image T, pixel tile, per_cu cap of the launcher (grid = budget x per_cu <= tiles), B = 2 except where noted.
+Persistent kernels (the conv1x1 rows: tests/common.py CONV1X1_GEOMETRY_ROUTES holds the instantiation, threads and pixel tile of each case as
+fdn_conv1x1_route reports them; test_conv1x1_geometry asserts them before it runs and the CPU suite pins them): tiles per image T, pixel tile, per_cu cap of the launcher (grid = budget x per_cu <= tiles), B = 2 except where noted.
 P = 84 x 131 = 11004 (P % 4 == 0: the 16-byte-lane forms) or 83 x 131 = 10873 (odd P: the scalar forms); W is never a tile multiple.
 
   case                     kernel (launcher)                          tile px  T/img  total  per_cu  tiles per workgroup at budget 1 / 2 / 3 / 7
@@ -51,7 +52,7 @@ import pytest
 import torch
 
 import fdn_oracle as O
-from common import assert_close_cond, rel_rms
+from common import CONV1X1_GEOMETRY_ROUTES, assert_close_cond, conv1x1_route_name, rel_rms
 
 pytestmark = pytest.mark.gpu
 F = torch.nn.functional
@@ -158,7 +159,7 @@ def test_cu_budget_bounds(ops):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# fdn_conv1x1, every form without a weight cache (the kernel each case reaches: the table at the top; csrc/gemm1x1.hip fdn_conv1x1)
+# fdn_conv1x1, every form without a weight cache (the kernel each case reaches: CONV1X1_GEOMETRY_ROUTES, asserted below; csrc/conv1x1_route.hpp)
 # ---------------------------------------------------------------------------------------------------------------------------------
 CONV1X1 = {   # name: K, N, H, W, prologue, epilogue, act, want_stats, x passed as a channel slice
     "smallk_res": (32, 152, 84, 131, "ln", "res", 0, False, True),
@@ -217,6 +218,8 @@ def test_conv1x1_geometry(ops, name):
         ref = ref * m.to(D) + a.to(D)
         kw["muladd"] = (dev(m), dev(a))
     wd, bd = dev(w), dev(bias)
+    rt = ops.conv1x1(xs, wd, bd, act=act, want_stats=want_stats, route_only=True, **kw)
+    assert (conv1x1_route_name(rt), rt["threads"], rt["tile_px"]) == CONV1X1_GEOMETRY_ROUTES[name], rt      # the kernel this case is here for
 
     def run():
         out = ops.conv1x1(xs, wd, bd, act=act, want_stats=want_stats, **kw)

@@ -378,7 +378,10 @@ def test_conv1x1_variants(A, K, N, H, W, pro):
         xin, xs = xd, dev(x)
     ref = torch.nn.functional.conv2d(xin, w.double().view(N, K, 1, 1)) + res.double()
     # without a weight cache: the fp32-MFMA kernels; with one: deep shapes (K, N >= 96) take the split-bf16 kernel (gemm_split.hip)
+    from common import CONV1X1_VARIANT_ROUTES, conv1x1_route_name
     for cache in (None, (ops.WeightCache(), "t")):
+        rt = ops.conv1x1(xs, dev(w), res=dev(res), want_stats=True, cache=cache, route_only=True, **kw)
+        assert conv1x1_route_name(rt) == CONV1X1_VARIANT_ROUTES[(K, N, H, W, pro)][cache is not None], rt      # the variant this case is here for
         got = ops.conv1x1(xs, dev(w), res=dev(res), want_stats=True, cache=cache, **kw)
         assert rel_rms(got.cpu(), ref) < 2e-6, cache
         mu, var = ref.mean(1), ref.var(1, unbiased=False)
@@ -435,9 +438,13 @@ def test_conv1x1_split_bf16_kernel(A, K, N, H, W, pro, epi):
         bias = _rnd(N, seed=9)
         ref = ref + bias.double().view(1, -1, 1, 1)
     want_stats = N <= 128 and K >= 96          # (the short-K strip form has no statistics epilogue: project_in convs do not need one)
+    from common import CONV1X1_SPLIT_ROUTES, conv1x1_route_name
     wc = ops.WeightCache()
+    rt = ops.conv1x1(xs, dev(w), None if bias is None else dev(bias), want_stats=want_stats, cache=(wc, "t"), route_only=True, **kw)
+    launches = fdn_hip.bf16_mfma_launches()
     got = ops.conv1x1(xs, dev(w), None if bias is None else dev(bias), want_stats=want_stats, cache=(wc, "t"), **kw)
     assert any(k.endswith(":pk") for k in wc._store), "the packed-weight path was not taken"
+    assert conv1x1_route_name(rt) == CONV1X1_SPLIT_ROUTES[(K, N, H, W, pro, epi)] and rt["bf16_pipe"] and fdn_hip.bf16_mfma_launches() > launches, rt
     plain = ops.conv1x1(xs, dev(w), None if bias is None else dev(bias), want_stats=want_stats, **kw)
     e_split, e_f32 = rel_rms(got.cpu(), ref), rel_rms(plain.cpu(), ref)
     assert e_split < 2e-6 and e_split < 1.5 * e_f32 + 2e-8, (e_split, e_f32)
@@ -458,10 +465,15 @@ def test_conv1x1_two_inputs_on_the_split_bf16_kernel(A, K0, K1, N, H, W):
     x0, x1 = _rnd(B, K0, H, W, seed=1), _rnd(B, K1, H, W, seed=2) * 0.7 + 0.1
     w, bias = _rnd(N, K0 + K1, seed=3) / (K0 + K1) ** 0.5, _rnd(N, seed=4)
     ref = torch.nn.functional.conv2d(torch.cat([x0, x1], 1).double(), w.double().view(N, -1, 1, 1), bias.double())
+    import fdn_hip
+    from common import CONV1X1_TWO_INPUT_ROUTES, conv1x1_route_name
     wc = ops.WeightCache()
     want = N <= 128
+    rt = ops.conv1x1([dev(x0), dev(x1)], dev(w), dev(bias), want_stats=want, cache=(wc, "t"), route_only=True)
+    launches = fdn_hip.bf16_mfma_launches()
     got = ops.conv1x1([dev(x0), dev(x1)], dev(w), dev(bias), want_stats=want, cache=(wc, "t"))
     assert any(k.endswith(":pk") for k in wc._store), "the packed-weight path was not taken"
+    assert conv1x1_route_name(rt) == CONV1X1_TWO_INPUT_ROUTES[(K0, K1, N, H, W)] and rt["bf16_pipe"] and fdn_hip.bf16_mfma_launches() > launches, rt
     plain = ops.conv1x1([dev(x0), dev(x1)], dev(w), dev(bias), want_stats=want)
     e_split, e_f32 = rel_rms(got.cpu(), ref), rel_rms(plain.cpu(), ref)
     assert e_split < 2e-6 and e_split < 1.5 * e_f32 + 2e-8, (e_split, e_f32)

@@ -539,3 +539,127 @@ def test_fft_route_argument_validation(lib):
     with pytest.raises(FdnHipError):
         ops.fft_route(ops.FFT_ROWS, 641)
     assert ops.fft_route(ops.FFT_COLS, 4097)["route"] == "refused"           # a refusal is an answer, not an error
+
+
+# ---- (ABI 22) the routes of fdn_conv1x1: fdn_conv1x1_route is host arithmetic on the descriptor, fdn_conv1x1 launches what it answers ----
+def _route_name(fields):
+    from common import conv1x1_route_name, conv1x1_route_of
+    return conv1x1_route_name(conv1x1_route_of(fields))
+
+
+def test_conv1x1_route_sweep_matches_the_recorded_routes(lib):
+    """tests/conv1x1_routes.txt: every descriptor of tools/gen_conv1x1_route_cases.py (K and N across every threshold of the route, odd /
+    huge P, prologues, epilogues, segments, bf16 storage, misaligned pointers and strides, both matrix-pipe modes) with the route the
+    if-ladder of fdn_conv1x1 took before the table existed.  Every line must still get that answer, field for field."""
+    import importlib.util
+    from common import CONV1X1_ROUTE_FIELDS, conv1x1_route_of
+    spec = importlib.util.spec_from_file_location("gen_conv1x1_route_cases", os.path.join(ROOT, "tools", "gen_conv1x1_route_cases.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    path = os.path.join(ROOT, "tests", "conv1x1_routes.txt")
+    assert os.path.getsize(path) < 200 * 1024
+    lines = [ln.split("|") for ln in open(path) if not ln.startswith("#")]
+    assert [a.strip() for a, _ in lines] == gen.cases()                    # the committed descriptors are the generator's
+    forms, wrong = set(), []
+    for a, b in lines:
+        want = tuple(int(v) for v in b.split())
+        got = conv1x1_route_of([int(v) for v in a.split()])
+        assert len(want) == len(CONV1X1_ROUTE_FIELDS)
+        forms.add((want[1], want[0]))
+        if got != want:
+            wrong.append((a.strip(), want, got))
+    assert not wrong, (len(wrong), wrong[:5])
+    # every form, and both kinds of refusal, are in the sweep
+    assert forms >= {(f, 0) for f in range(1, 11)} | {(0, 1), (0, 4)}, sorted(forms)
+
+
+def test_conv1x1_route_pins_the_network_shapes(lib):
+    from common import CONV1X1_NET_ROUTES, conv1x1_fields
+    P = 84 * 131
+    for what, kw, plain, packed in CONV1X1_NET_ROUTES:
+        kw = dict({"P": P}, **kw)
+        assert _route_name(conv1x1_fields(**kw)) == plain, what
+        assert _route_name(conv1x1_fields(wpk=1, **kw)) == (packed or plain), what
+        for wpk in (0, 1):                                           # the f32 pipe: no split-bf16 form, packed weights or not
+            assert _route_name(conv1x1_fields(wpk=wpk, pipe=1, **kw)) == plain, what
+
+
+def test_conv1x1_route_pins_the_cases_of_the_gpu_tests(lib):
+    """Each conv1x1 case of tests/test_gpu_geometry.py and tests/test_gpu_parity.py still reaches the kernel it was chosen for (the GPU tests
+    assert the same on the descriptor they really pass)."""
+    import importlib
+    from common import (CONV1X1_GEOMETRY_ROUTES, CONV1X1_SPLIT_ROUTES, CONV1X1_TWO_INPUT_ROUTES, CONV1X1_VARIANT_ROUTES, conv1x1_fields,
+                        conv1x1_route_name, conv1x1_route_of)
+    cases = importlib.import_module("test_gpu_geometry").CONV1X1
+    assert set(cases) == set(CONV1X1_GEOMETRY_ROUTES)
+    for name, (K, N, H, W, pro, epi, act, want_stats, _sliced) in cases.items():
+        rt = conv1x1_route_of(conv1x1_fields(K, N, H * W, pro, epi, act=act, so=int(want_stats)))
+        assert (conv1x1_route_name(rt), rt[11], rt[12]) == CONV1X1_GEOMETRY_ROUTES[name], name
+    assert len({r[0] for r in CONV1X1_GEOMETRY_ROUTES.values()}) == len(CONV1X1_GEOMETRY_ROUTES)        # no two cases on one instantiation
+    for (K, N, H, W, pro), (plain, cached) in CONV1X1_VARIANT_ROUTES.items():
+        for wpk, want in ((0, plain), (1, cached)):
+            assert _route_name(conv1x1_fields(K, N, H * W, pro, "res", so=int(N <= 160), wpk=wpk)) == want, (K, N, pro, wpk)
+    for (K, N, H, W, pro, epi), want in CONV1X1_SPLIT_ROUTES.items():
+        assert want.startswith("split")
+        assert _route_name(conv1x1_fields(K, N, H * W, pro, epi, so=int(N <= 128 and K >= 96), wpk=1)) == want, (K, N, pro, epi)
+    for (K0, K1, N, H, W), want in CONV1X1_TWO_INPUT_ROUTES.items():
+        assert _route_name(conv1x1_fields(K0 + K1, N, H * W, segs=(K0, K1), so=int(N <= 128), wpk=1, B=2 if H < 100 else 1)) == want, (K0, K1, N)
+
+
+def test_conv1x1_route_argument_validation(lib):
+    from common import CONV1X1_ROUTE_FIELDS, conv1x1_case_desc, conv1x1_fields
+    from fdn_hip import ops
+    nd = len(CONV1X1_ROUTE_FIELDS)
+    desc = (ctypes.c_int * nd)()
+    d, _ = conv1x1_case_desc(conv1x1_fields(32, 152, 84 * 131, "ln"))
+    assert lib.fdn_conv1x1_route(ctypes.byref(d), desc, nd) == 0 and desc[0] == 0 and ops.CONV1X1_FORMS[desc[1]] == "smallk_vec"
+    assert lib.fdn_conv1x1_route(None, desc, nd) == 1
+    assert lib.fdn_conv1x1_route(ctypes.byref(d), None, nd) == 1
+    assert lib.fdn_conv1x1_route(ctypes.byref(d), desc, nd - 1) == 1
+    assert lib.fdn_conv1x1(None, None) == 1
+
+    def status(change, **kw):
+        d, _ = conv1x1_case_desc(conv1x1_fields(**dict(dict(K=64, N=64, P=4096), **kw)))
+        change(d)
+        rt = ops.conv1x1_route(d)                                    # a refusal is an answer, not an exception
+        if rt["status"]:
+            assert rt["form"] == "refused" and not any(rt[k] for k in CONV1X1_ROUTE_FIELDS[2:]), rt
+        return rt["status"]
+    ARG, UNSUPPORTED = 1, 4
+    assert status(lambda d: None) == 0
+    for field in ("B", "K", "N", "P"):
+        assert status(lambda d: setattr(d, field, 0)) == ARG, field
+    for field in ("w", "out"):
+        assert status(lambda d: setattr(d, field, None)) == ARG, field
+
+    def no_x0(d):
+        d.x[0] = None
+    assert status(no_x0) == ARG
+
+    def bad_segments(d):
+        d.kseg[0] = 60
+    assert status(bad_segments) == ARG                               # the segments do not add up to K
+
+    def segment_without_tensor(d):
+        d.x[1] = None
+    assert status(segment_without_tensor, segs=(32, 32)) == ARG
+    assert status(lambda d: setattr(d, "stats", None), pro="ln") == ARG              # only LN3_GATE / LN_MULADD may leave the statistics to the kernel
+    assert status(lambda d: setattr(d, "gamma", None), pro="muladd") == ARG
+    assert status(lambda d: setattr(d, "xb", None), pro="muladd") == ARG
+    assert status(lambda d: setattr(d, "ln_group", 21), K=66, pro="ln3") == ARG      # 3 * ln_group != K
+    assert status(lambda d: setattr(d, "res", None), epi="res") == ARG
+    assert status(lambda d: setattr(d, "add", None), epi="muladd") == ARG
+    assert status(lambda d: None, N=161, so=1) == ARG                                # statistics epilogue: N <= 160
+    assert status(lambda d: setattr(d, "pro", 7)) == ARG                             # no such prologue (the generic form's switch)
+    # refusals: 32-bit offsets, odd segments, bf16 storage without a form, statistics no kernel of the shape takes itself
+    assert status(lambda d: None, K=64, N=64, P=12_000_000) == UNSUPPORTED           # (N + 200) planes past 4 GiB
+    assert status(lambda d: None, K=345, N=64, P=3_000_000) == UNSUPPORTED           # (K + 40) planes past 4 GiB
+    assert status(lambda d: None, K=66, N=64, segs=(33, 33)) == UNSUPPORTED
+    assert status(lambda d: None, xbf=1, obf=1) == UNSUPPORTED
+    assert status(lambda d: None, K=64, N=64, pro="ln", xbf=1) == UNSUPPORTED
+    assert status(lambda d: None, K=128, N=128, pro="muladd", epi="muladd", st=0) == UNSUPPORTED            # no packed weights
+    assert status(lambda d: None, K=128, N=128, pro="muladd", epi="muladd", st=0, wpk=1) == 0
+    assert status(lambda d: None, K=128, N=128, pro="muladd", epi="muladd", st=0, wpk=1, pipe=0, P=4_200_000) == UNSUPPORTED   # 2^31 mask offset
+    # the pointer values are read, never what they point to: the same descriptor at 4 bytes off takes the dword form
+    d, _ = conv1x1_case_desc(conv1x1_fields(32, 152, 84 * 131, "ln")[:15] + [1, 0])
+    assert ops.conv1x1_route(d)["form"] == "smallk"

@@ -136,7 +136,7 @@ def test_weighted_entry_points_validate_arguments_without_gpu(lib):
     """NULL pointers / bad sizes are rejected before any launch (FDN_ERR_ARG = 1); the ABI version has not moved"""
     import ctypes
     import fdn_hip
-    assert lib.fdn_abi_version() == fdn_hip.ABI_VERSION == 21
+    assert lib.fdn_abi_version() == fdn_hip.ABI_VERSION == 22
     p = ctypes.c_void_p(64)                          # never dereferenced: every call below fails its argument check
     for f, mid in ((lib.fdn_tiles_merge_w, (3,)), (lib.fdn_tiles_merge_w_u8, ())):
         def call(ptrs=(p, p, p, p, p), T=4, h=70, w=90, ch=64, cw=64):
@@ -163,7 +163,7 @@ def test_abi_table_holds_the_new_entry_points():
     assert PROTOTYPES["fdn_tiles_merge_w_u8"] == ("I", ["P"] * 5 + ["I"] * 6 + ["P"])
     assert ARG_NAMES["fdn_tiles_merge_w"] == ["tiles", "out", "ij", "wy", "wx", "T", "C", "H", "W", "ch", "cw", "stream"]
     assert ARG_NAMES["fdn_tiles_merge_w_u8"] == ["tiles", "out", "ij", "wy", "wx", "T", "h", "w", "ch", "cw", "swap_rb", "stream"]
-    assert len(PROTOTYPES) == 73
+    assert len(PROTOTYPES) == 74
 
 
 def test_blend_keyword_is_checked_before_anything_runs(lib):

@@ -105,7 +105,7 @@ def test_u8_tile_entry_points_validate_arguments_without_gpu(lib):
     """NULL pointers / bad sizes are rejected before any launch (FDN_ERR_ARG = 1)"""
     import ctypes
     import fdn_hip
-    assert lib.fdn_abi_version() == fdn_hip.ABI_VERSION == 21
+    assert lib.fdn_abi_version() == fdn_hip.ABI_VERSION == 22
     p = ctypes.c_void_p(64)                          # never dereferenced: every call below fails its argument check
     for f in (lib.fdn_tiles_gather_u8, lib.fdn_tiles_merge_u8):
         assert f(None, p, p, 4, 70, 90, 64, 64, 1, None) == 1

@@ -35,7 +35,7 @@ def test_versions_and_prototype_table(lib):
     import fdn_hip
     from fdn_hip import _abi, _abi_temporal, _abi_video, _abi_vmetrics
     assert lib.fdn_vmetrics_abi_version() == fdn_hip.VMETRICS_ABI_VERSION == 1
-    assert lib.fdn_abi_version() == fdn_hip.ABI_VERSION == 21 and len(_abi.PROTOTYPES) == 73
+    assert lib.fdn_abi_version() == fdn_hip.ABI_VERSION == 22 and len(_abi.PROTOTYPES) == 74
     assert lib.fdn_video_abi_version() == fdn_hip.VIDEO_ABI_VERSION == 1 and len(_abi_video.PROTOTYPES) == 3
     assert lib.fdn_temporal_abi_version() == fdn_hip.TEMPORAL_ABI_VERSION == 1 and len(_abi_temporal.PROTOTYPES) == 3
     spec = importlib.util.spec_from_file_location("gen_abi_table", os.path.join(ROOT, "tools", "gen_abi_table.py"))

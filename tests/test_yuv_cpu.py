@@ -29,7 +29,7 @@ def test_versions_and_prototype_tables(lib):
     import fdn_hip
     from fdn_hip import _abi, _abi_video
     assert lib.fdn_video_abi_version() == fdn_hip.VIDEO_ABI_VERSION == 1
-    assert lib.fdn_abi_version() == fdn_hip.ABI_VERSION == 21 and len(_abi.PROTOTYPES) == 73
+    assert lib.fdn_abi_version() == fdn_hip.ABI_VERSION == 22 and len(_abi.PROTOTYPES) == 74
     spec = importlib.util.spec_from_file_location("gen_abi_table", os.path.join(ROOT, "tools", "gen_abi_table.py"))
     gen = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(gen)
