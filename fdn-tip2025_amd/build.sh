@@ -11,7 +11,7 @@ mkdir -p fdn_hip "$BUILD"
 NOSLP="patchfft ffn_tail fdsa_full"
 OBJS=""
 PIDS=""
-NEWEST_HDR=$(ls -t csrc/*.hpp csrc/*.inc ../include/fdn_hip.h ../include/fdn_video.h ../include/fdn_temporal.h ../include/fdn_vmetrics.h ../include/fdn_ensemble.h build.sh | head -1)
+NEWEST_HDR=$(ls -t csrc/*.hpp csrc/*.inc ../include/fdn_hip.h ../include/fdn_video.h ../include/fdn_temporal.h ../include/fdn_vmetrics.h ../include/fdn_ensemble.h ../include/fdn_spectral.h build.sh | head -1)
 for f in csrc/*.hip; do
   n=$(basename "${f%.hip}")
   o=$BUILD/$n.o

@@ -17,6 +17,8 @@
 #include "common.hpp"
 #include "fft_regs.hpp"
 
+#include "../../include/fdn_spectral.h"
+
 namespace {
 
 constexpr int MAX_STAGES = FDN_FFT_MAX_STAGES;    // fdn_fft_route reports up to this many stages
@@ -537,7 +539,7 @@ __global__ __launch_bounds__(NT) void irfft_rows_kernel(const float2* __restrict
 // ------------------------------------------------------------------------------------------
 struct ColArgs {
     // spectrum planes: [planes][H][Wf] complex
-    float2* z;                 // in/out (FCAFFN), in (fwd), out (inv polar)
+    float2* z;                 // in/out (FCAFFN, c2c), in (fwd), out (inv polar)
     int H, Wf, C;              // C = channels per batch item (plane = b*C + c)
     int tc, tcs;               // columns per workgroup (a power of two) and its log2
     long planes;               // total planes (a multiple of C)
@@ -556,7 +558,7 @@ struct ColArgs {
     int Hin, Wfin;
 };
 
-enum { COL_FCAFFN = 0, COL_FWD = 1, COL_INV_POLAR = 2 };
+enum { COL_FCAFFN = 0, COL_FWD = 1, COL_INV_POLAR = 2, COL_C2C = 3 };    // COL_C2C: forward, the complex spectrum back in place (generic kernel only)
 
 template <int MODE, int BIG, bool INPL>
 __global__ __launch_bounds__(NT, (INPL ? 2 : 1)) void fft_cols_kernel(ColArgs a, const Plan p) {
@@ -647,6 +649,15 @@ __global__ __launch_bounds__(NT, (INPL ? 2 : 1)) void fft_cols_kernel(ColArgs a,
             const long o = ((long)plane * H + h) * Wf + col;
             if (a.out_abs) a.out_abs[o] = cabs2(v);
             if (a.out_ang) a.out_ang[o] = atan2f(v.y, v.x);
+        }
+        return;
+    }
+
+    if (MODE == COL_C2C) {
+#pragma unroll 8
+        for (int idx = threadIdx.x; idx < per; idx += NT) {
+            const int h = idx >> tcs, c = idx & tcm;
+            if (c < ncol) zp[(long)h * Wf + col0 + c] = Z[idx];
         }
         return;
     }
@@ -1220,13 +1231,10 @@ int launch_cols_k(ColArgs a, const Plan& p, long planes, size_t lds, fdn_stream_
     return fdn_launch_status();
 }
 
+// the generic kernel on the generic route r of its length (FDN_FFT_INPLACE / _PINGPONG)
 template <int MODE>
-int launch_cols(ColArgs a, long planes, fdn_stream_t stream) {
-    Route r;
-    cols_route(a.H, &r);
+int launch_cols_generic(ColArgs a, const Route& r, long planes, fdn_stream_t stream) {
     if (r.kind == FDN_FFT_REFUSED) return FDN_ERR_UNSUPPORTED;
-    if (r.kind == FDN_FFT_PLANNED)
-        return col_plan(a.H, [&](auto R, auto P) { return launch_cols_rp<decltype(R)::value, decltype(P)::value, MODE>(a, planes, stream); });
     Plan p;
     if (!make_plan(a.H, a.H, &p)) return FDN_ERR_UNSUPPORTED;
     a.tc = r.width;
@@ -1236,6 +1244,15 @@ int launch_cols(ColArgs a, long planes, fdn_stream_t stream) {
         constexpr int V = decltype(v)::value;
         return launch_cols_k<MODE, V % 4, V / 4 != 0>(a, p, planes, r.lds, stream);
     });
+}
+
+template <int MODE>
+int launch_cols(ColArgs a, long planes, fdn_stream_t stream) {
+    Route r;
+    cols_route(a.H, &r);
+    if (r.kind == FDN_FFT_PLANNED)
+        return col_plan(a.H, [&](auto R, auto P) { return launch_cols_rp<decltype(R)::value, decltype(P)::value, MODE>(a, planes, stream); });
+    return launch_cols_generic<MODE>(a, r, planes, stream);
 }
 
 template <int R1, int P>
@@ -1442,4 +1459,16 @@ extern "C" int fdn_fft_cols_inv_polar(const float* mag, const float* pha, int Hi
     a.H = H; a.Wf = Wf; a.C = 1;
     a.in_mag = mag; a.in_pha = pha; a.Hin = Hin; a.Wfin = Wfin;
     return launch_cols<COL_INV_POLAR>(a, planes, stream);
+}
+
+// include/fdn_spectral.h: the forward column pass that hands out the complex spectrum.  Not a per-step kernel: it runs the generic
+// kernel on the generic route of every length, so the compile-time plans gain no instantiation.
+extern "C" int fdn_fft_cols_c2c(float* z, long planes, int H, int Wf, fdn_stream_t stream) {
+    FDN_CHECK_ARG(z && planes > 0 && H > 0 && Wf > 0);
+    ColArgs a = {};
+    a.z = reinterpret_cast<float2*>(z);
+    a.H = H; a.Wf = Wf; a.C = 1;
+    Route r;
+    cols_route_generic(H, &r);
+    return launch_cols_generic<COL_C2C>(a, r, planes, stream);
 }

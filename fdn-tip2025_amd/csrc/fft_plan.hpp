@@ -307,12 +307,11 @@ int planned_route(Route* r, int N, int R, int P, int width) {
     return FDN_OK;
 }
 
-// columns of length H: its compile-time plan, else in-place passes if every radix has an in-place butterfly and fits, else
-// ping-pong passes with pick_tc columns per workgroup; refused when no tc fits or the buffers plus the twiddle table exceed
-// the LDS of a workgroup
-void cols_route(int H, Route* r) {
+// columns of length H on the generic kernel: in-place passes if every radix has an in-place butterfly and fits, else ping-pong
+// passes with pick_tc columns per workgroup; refused when no tc fits or the buffers plus the twiddle table exceed the LDS of a
+// workgroup
+void cols_route_generic(int H, Route* r) {
     *r = Route{};
-    if (col_plan(H, [&](auto R, auto P) { return planned_route(r, H, R, P, 256 / P); }) == FDN_OK) return;
     if (!plan_radices(H, &r->p)) return;
     const int itc = inplace_tc(r->p, H);
     if (itc > 0) {
@@ -329,6 +328,13 @@ void cols_route(int H, Route* r) {
     r->width = tc;
     r->big = plan_big2(r->p) ? 2 : plan_big(r->p) ? 1 : 0;
     r->lds = lds;
+}
+
+// columns of length H: its compile-time plan, else the generic route (fdn_fft_cols_c2c takes the generic route for every length)
+void cols_route(int H, Route* r) {
+    *r = Route{};
+    if (col_plan(H, [&](auto R, auto P) { return planned_route(r, H, R, P, 256 / P); }) == FDN_OK) return;
+    cols_route_generic(H, r);
 }
 
 // rows of width W (half-length M = W / 2): the compile-time plan if the caller's buffers allow its 8-byte accesses

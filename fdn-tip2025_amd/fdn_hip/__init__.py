@@ -1,5 +1,5 @@
 """ctypes binding of libfdn_hip.so (the C ABI declared in include/fdn_hip.h, include/fdn_video.h, include/fdn_temporal.h,
-include/fdn_vmetrics.h and include/fdn_ensemble.h).
+include/fdn_vmetrics.h, include/fdn_ensemble.h and include/fdn_spectral.h).
 
 PyTorch is plumbing here: it owns device memory and the current HIP stream; every compute step
 of the FDN path is a call into the library.  There is NO CPU or eager fallback: if the shared
@@ -43,6 +43,7 @@ VIDEO_ABI_VERSION = 1   # include/fdn_video.h (the video frame entry points), li
 TEMPORAL_ABI_VERSION = 1  # include/fdn_temporal.h (the ratio filter across frames), likewise
 VMETRICS_ABI_VERSION = 1  # include/fdn_vmetrics.h (video evaluation from codec samples), likewise
 ENSEMBLE_ABI_VERSION = 1  # include/fdn_ensemble.h (the flipped and transposed copies of the self-ensemble), likewise
+SPECTRAL_ABI_VERSION = 1  # include/fdn_spectral.h (Fourier evaluation: the complex spectrum, the error per band in amplitude and phase), likewise
 
 
 def lib_path():
@@ -79,6 +80,10 @@ def lib():
             v = _lib.fdn_ensemble_abi_version()
             _lib = None
             raise ImportError(f"{_LIB_PATH} has ensemble ABI version {v}, this binding needs {ENSEMBLE_ABI_VERSION}: rebuild with build.sh")
+        if _lib.fdn_spectral_abi_version() != SPECTRAL_ABI_VERSION:
+            v = _lib.fdn_spectral_abi_version()
+            _lib = None
+            raise ImportError(f"{_LIB_PATH} has spectral ABI version {v}, this binding needs {SPECTRAL_ABI_VERSION}: rebuild with build.sh")
     return _lib
 
 
@@ -90,8 +95,9 @@ def _declare(l, missing_ok=False):
     from ._abi_temporal import PROTOTYPES as TEMPORAL_PROTOTYPES
     from ._abi_vmetrics import PROTOTYPES as VMETRICS_PROTOTYPES
     from ._abi_ensemble import PROTOTYPES as ENSEMBLE_PROTOTYPES
+    from ._abi_spectral import PROTOTYPES as SPECTRAL_PROTOTYPES
     kinds = {"P": ctypes.c_void_p, "I": ctypes.c_int, "L": ctypes.c_long, "F": ctypes.c_float, "DESC": ctypes.POINTER(Conv1x1Desc)}
-    tables = (PROTOTYPES, VIDEO_PROTOTYPES, TEMPORAL_PROTOTYPES, VMETRICS_PROTOTYPES, ENSEMBLE_PROTOTYPES)
+    tables = (PROTOTYPES, VIDEO_PROTOTYPES, TEMPORAL_PROTOTYPES, VMETRICS_PROTOTYPES, ENSEMBLE_PROTOTYPES, SPECTRAL_PROTOTYPES)
     for name, (ret, sig) in [item for t in tables for item in t.items()]:
         f = getattr(l, name, None) if missing_ok else getattr(l, name)      # AttributeError: the library lacks a symbol the header declares
         if f is None:

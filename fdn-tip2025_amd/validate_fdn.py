@@ -16,7 +16,9 @@ the ratio is taken per tile as the reference does after grids() (--tile-ratio ti
 frame), and the merged 8-bit frame is scored.  The csv then holds one ratio per tile, joined by ';'.  --tile-blend feather merges the
 tiles with ramps across their overlaps instead of the reference's average (not what the reference scores).  --ensemble 2|4|8 scores the
 geometric self-ensemble (fdn_hip.ensemble; not what the reference scores either): FDN on that many flipped / transposed copies of every
-frame or tile, all fed the ratio of the untransformed one, averaged.
+frame or tile, all fed the ratio of the untransformed one, averaged.  --fourier appends the Fourier figures of fdn_hip.spectral to every
+line and to the csv (calculate_fourier_metrics.py has what they mean): the amplitude, phase and zero-frequency share of the MSE of the whole
+8-bit frame (no crop_border; the width must be even), the reference's FFTLoss, and per band the columns of that tool's csv.
 """
 import argparse
 import glob
@@ -66,7 +68,11 @@ def parse_args(argv=None):
     from inference_fdn_lolblur import add_ensemble_arg, add_tile_args
     add_tile_args(ap, ratio_default="tile")
     add_ensemble_arg(ap)
+    ap.add_argument("--fourier", action="store_true", help="also split every frame's error into amplitude and phase per frequency band")
+    ap.add_argument("--fourier-bands", type=int, default=8, help="radial frequency bands besides the zero-frequency bin (1 .. 32)")
     a = ap.parse_args(argv)
+    if not 1 <= a.fourier_bands <= 32:
+        ap.error("--fourier-bands must be in 1 .. 32")
     if a.ratio == "lpnet" and not a.lpnet:
         ap.error("--ratio lpnet needs --lpnet")
     if a.crop_border < 0:
@@ -90,6 +96,10 @@ def main(argv=None):
     else:
         from basicsr.models.archs.fdnlol24_arch import FDN_lolv1 as Net
 
+    if a.fourier:
+        from calculate_fourier_metrics import SUMMARY_KEYS, fourier_line, mean_of
+        from fdn_hip import FdnHipError, spectral
+
     dev = torch.device(a.device)
     torch.cuda.set_device(dev)
     net = Net().to(dev).eval()
@@ -101,7 +111,7 @@ def main(argv=None):
     mode = RATIO_MODE[(a.ratio, a.variant)]
 
     n = len(a.pairs)
-    psnr, ssim, ratio = [None] * n, [None] * n, [None] * n
+    psnr, ssim, ratio, fourier = [None] * n, [None] * n, [None] * n, [None] * n
     with ThreadPoolExecutor(max_workers=4) as pool:
         writers = []
         for idx, lqs, gts in decoded_groups(a.pairs, a.batch, pool):
@@ -113,22 +123,32 @@ def main(argv=None):
                                        ensemble=a.ensemble)
             r = r.reshape(r.shape[0], -1).cpu().tolist()              # one ratio per frame, or one per tile of a tiled frame
             frames = out.cpu().numpy() if a.dest else None
+            if a.fourier:
+                try:
+                    fm = spectral.calculate_fourier(out, gt, bands=a.fourier_bands, bgr=False)
+                except FdnHipError as e:
+                    sys.exit(f"validate_fdn.py: --fourier: {e}")
             for k, i in enumerate(idx):
                 psnr[i], ssim[i], ratio[i] = p[k], s[k], r[k]
+                if a.fourier:
+                    fourier[i] = fm[k]
                 if a.dest:
                     writers.append(pool.submit(write_rgb, a.dest[i], frames[k]))
         for w in writers:
             w.result()
     for i, (lq_path, _) in enumerate(a.pairs):
         basename = os.path.splitext(os.path.basename(lq_path))[0]
-        print(f'{i+1:3d}: {basename:25}. \tPSNR: {psnr[i]:.6f} dB, \tSSIM: {ssim[i]:.6f}')
-    print(f'Average: PSNR: {sum(psnr) / n:.6f} dB, SSIM: {sum(ssim) / n:.6f}')
+        tail = f", \t{fourier_line(fourier[i])}" if a.fourier else ""
+        print(f'{i+1:3d}: {basename:25}. \tPSNR: {psnr[i]:.6f} dB, \tSSIM: {ssim[i]:.6f}{tail}')
+    tail = ", " + fourier_line({k: mean_of([m[k] for m in fourier]) for k in SUMMARY_KEYS}) if a.fourier else ""
+    print(f'Average: PSNR: {sum(psnr) / n:.6f} dB, SSIM: {sum(ssim) / n:.6f}{tail}')
     if a.csv:
         os.makedirs(os.path.dirname(a.csv) or ".", exist_ok=True)
         with open(a.csv, "w") as f:
-            f.write("frame,psnr,ssim,ratio\n")
-            for (lq_path, _), p, s, r in zip(a.pairs, psnr, ssim, ratio):
-                f.write(f"{lq_path},{p!r},{s!r},{';'.join(repr(v) for v in r)}\n")
+            f.write("frame,psnr,ssim,ratio" + ("," + ",".join(spectral.csv_header(a.fourier_bands)) if a.fourier else "") + "\n")
+            for i, ((lq_path, _), p, s, r) in enumerate(zip(a.pairs, psnr, ssim, ratio)):
+                tail = "," + ",".join(spectral.csv_row(fourier[i])) if a.fourier else ""
+                f.write(f"{lq_path},{p!r},{s!r},{';'.join(repr(v) for v in r)}{tail}\n")
     if a.dest:
         print(f"{n} frames -> {a.output}")
 

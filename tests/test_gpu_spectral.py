@@ -1,0 +1,348 @@
+"""GPU: the Fourier evaluation (include/fdn_spectral.h, fdn_hip.spectral, calculate_fourier_metrics.py, validate_fdn.py --fourier) against
+torch.fft in float64 and the float64 restatement of tests/spectral_ref.py.
+
+Shapes, the smallest that can go wrong: (2,2) has empty bands, (7,10) and (45,64) an odd H, W/2 + 1 = 6 / 20 / 33 / 81 is no multiple of the
+64 bins a wave takes per step nor of the column tiles, (96,160) has more than one group of rows per plane and more than one step per row;
+the column pass also runs one length per distinct route fdn_fft_route reports up to 800 (184 has a compile-time plan, which the c2c pass
+does not use; 66, 143 and 374 take the gather pass); planes 1 and 6.
+
+Tolerances.  The column pass: tests/test_gpu_fft_generic.py's criterion per line.  The band sums on given spectra: 1e-12 relative (float64
+arithmetic and the order of summation are all that differ).  End to end: each entry's worst band may be 4 times as far from the float64
+truth as the same formula on torch.fft.rfft2 in float32 is, plus 1e-6 - the float32 figure is computed here, per case."""
+import ctypes
+import json
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import spectral_ref as ref
+from common import GOLDEN, fdn_weights
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "fdn-tip2025_amd")
+
+SHAPES = [(2, 2), (7, 10), (34, 38), (45, 64), (96, 160)]
+# one length per distinct (route, BIG, gather pass) among the column lengths up to 800
+ROUTE_H = {120: ("inplace", 0, False), 322: ("inplace", 1, False), 184: ("planned", 0, False), 66: ("pingpong", 0, True),
+           784: ("pingpong", 0, False), 782: ("pingpong", 1, False), 374: ("pingpong", 1, True), 296: ("pingpong", 2, False),
+           143: ("pingpong", 2, True)}
+BANDS = [1, 8, 32]
+WORST = {}
+
+
+@pytest.fixture(scope="module")
+def S():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a ROCm GPU")
+    import fdn_hip
+    fdn_hip.lib()
+    from fdn_hip import spectral
+    yield spectral
+    for k in sorted(WORST):
+        print(f"worst  {k:40s} {WORST[k]:.3e}")
+
+
+def cuda(a):
+    return (torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a).to("cuda:0").contiguous()
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+# ---------------------------------------------------------------- 1  the column pass
+def test_route_lengths_cover_every_route(S):
+    """host arithmetic: ROUTE_H names one length for every (route, BIG, gather) fdn_fft_route reports for the lengths 1 .. 800"""
+    from fdn_hip import ops
+    seen = {}
+    for H in range(1, 801):
+        r = ops.fft_route(ops.FFT_COLS, H)
+        seen.setdefault((r["route"], r["big"], bool(r["gather"])), H)
+    for H, key in ROUTE_H.items():
+        r = ops.fft_route(ops.FFT_COLS, H)
+        assert (r["route"], r["big"], bool(r["gather"])) == key, (H, r)
+    assert set(ROUTE_H.values()) == set(seen), sorted(set(seen) - set(ROUTE_H.values()))
+
+
+def _per_line(got, ref32, truth, dims, what):
+    """tests/test_gpu_fft_generic.py's criterion: rel-RMS error of every line <= 4 err(fp32 torch) + 2e-6"""
+    got, ref32, truth = got.double().cpu(), ref32.double().cpu(), truth.double().cpu()
+    norm = (truth ** 2).sum(dims).sqrt() + 1e-300
+    e_got = ((got - truth) ** 2).sum(dims).sqrt() / norm
+    e_ref = ((ref32 - truth) ** 2).sum(dims).sqrt() / norm
+    bad = e_got > 4 * e_ref + 2e-6
+    print(f"{what}: worst line {e_got.max().item():.3e} (fp32 torch {e_ref.max().item():.3e})")
+    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.numel()} lines, worst {e_got.max().item():.3e} (fp32 torch {e_ref.max().item():.3e})"
+    WORST["cols c2c per-line rel-RMS"] = max(WORST.get("cols c2c per-line rel-RMS", 0.0), e_got.max().item())
+
+
+@pytest.mark.parametrize("planes", [1, 6])
+@pytest.mark.parametrize("H", sorted(ROUTE_H) + sorted({h for h, _ in SHAPES}))
+def test_cols_c2c(S, H, planes):
+    """fdn_fft_cols_c2c in place on random spectra with a ragged last column tile, against torch.fft.fft in float64, line by line"""
+    from fdn_hip import ops
+    lib, Wf = ops.lib(), 2 * 32 + 3 if H < 400 else 2 * 8 + 3            # more than one tile at every tc the routes pick, the last ragged
+    z = torch.randn(planes, H, Wf, 2, generator=torch.Generator().manual_seed(1000 * H + planes))
+    zd = cuda(z)
+    assert lib.fdn_fft_cols_c2c(_ptr(zd), ctypes.c_long(planes), H, Wf, ops.stream()) == 0
+    truth = torch.fft.fft(torch.view_as_complex(z.double()), dim=1)
+    ref32 = torch.fft.fft(torch.view_as_complex(z), dim=1)
+    _per_line(zd, torch.view_as_real(ref32), torch.view_as_real(truth), (1, 3), f"c2c H {H} planes {planes}")
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_rfft2(S, shape):
+    """rfft2 = fdn_rfft_rows + fdn_fft_cols_c2c against torch.fft.rfft2 in float64, per column; DC stays exactly real"""
+    H, W = shape
+    x = torch.rand(2, 3, H, W, generator=torch.Generator().manual_seed(H * W))
+    got = S.rfft2(cuda(x))
+    assert got.dtype == torch.complex64 and tuple(got.shape) == (2, 3, H, W // 2 + 1)
+    truth, ref32 = torch.fft.rfft2(x.double()), torch.fft.rfft2(x)
+    _per_line(torch.view_as_real(got), torch.view_as_real(ref32), torch.view_as_real(truth), (2, 4), f"rfft2 {H}x{W}")
+    assert (got.imag[..., 0, 0] == 0).all()
+
+
+# ---------------------------------------------------------------- 2  the band sums on given spectra
+@pytest.mark.parametrize("planes", [1, 6])
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_pair_bands_on_given_spectra(S, shape, planes):
+    """float32 spectra, dense and with a padded pitch whose padding holds NaN: 1e-12 relative per entry against the restatement fed the
+    same spectra; a band without a bin is exactly 0"""
+    H, W = shape
+    Wf = W // 2 + 1
+    g = torch.Generator().manual_seed(H * 31 + W + planes)
+    za = torch.randn(planes, H, Wf, 2, generator=g) * 3
+    zb = za * (0.5 + torch.rand(planes, H, Wf, 1, generator=g)) + 0.3 * torch.randn(planes, H, Wf, 2, generator=g)
+    ca, cb = torch.view_as_complex(za).numpy(), torch.view_as_complex(zb).numpy()
+    pitch = Wf + 5
+    pa, pb = (torch.full((planes, H, pitch, 2), float("nan")) for _ in range(2))
+    pa[:, :, :Wf], pb[:, :, :Wf] = za, zb
+    for nb in BANDS:
+        want = ref.spectrum_sums(ca, cb, H, W, nb)
+        counts = ref.band_counts(H, W, nb)
+        for what, (xa, xb) in (("dense", (za, zb)), ("padded", (pa, pb))):
+            got = S.spectrum_pair_bands(cuda(xa), cuda(xb), H, W, nb).cpu().numpy()
+            assert got.shape == (planes, nb + 1, 5) and np.isfinite(got).all(), what
+            err = np.abs(got - want) / np.where(want != 0, np.abs(want), 1.0)
+            print(f"{H}x{W} planes {planes} nb {nb} {what}: worst relative difference {err.max():.3e}")
+            assert (err <= 1e-12).all(), (what, nb, err.max())
+            for b in range(nb + 1):
+                if counts[b] == 0:
+                    assert (got[:, b] == 0).all() and not np.signbit(got[:, b]).any(), (nb, b)
+        if shape == (2, 2) and nb == 8:
+            assert counts == [1, 0, 0, 0, 0, 0, 0, 0, 3]
+
+
+# ---------------------------------------------------------------- 3 .. 7  image pairs end to end
+def _pairs(H, W, B, seed):
+    """textured 8-bit images scaled by 1/255 -> {name: (restored, ground truth)} float32 [B][3][H][W]: a gain error plus strong noise, and
+    a pair near 45 dB (a little more than half of the codes off by up to 3)"""
+    g = np.random.default_rng(seed)
+    gt = ref.textured(H, W, seed, n=B)
+    noisy = np.clip(np.rint(0.8 * gt + g.normal(0.0, 20.0, gt.shape)), 0, 255).astype(np.uint8)
+    near = np.clip(gt.astype(np.int64) + (g.random(gt.shape) < 0.55) * g.integers(-3, 4, gt.shape), 0, 255).astype(np.uint8)
+    f = lambda u: np.ascontiguousarray(u.transpose(0, 3, 1, 2)).astype(np.float32) / np.float32(255)
+    return {"gain+noise": (f(noisy), f(gt)), "near 45 dB": (f(near), f(gt))}
+
+
+def _worst_band_error(s, truth):
+    """per entry the worst relative error over planes and bands; a band that is 0 in truth must be 0"""
+    s, truth = np.asarray(s).reshape(-1, *truth.shape[-2:]), truth.reshape(-1, *truth.shape[-2:])
+    zero = truth == 0
+    assert (s[zero] == 0).all()
+    return (np.abs(s - truth) / np.where(zero, 1.0, np.abs(truth))).max(axis=(0, 1))
+
+
+@pytest.mark.parametrize("B", [1, 2])
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_pair_bands_end_to_end(S, shape, B):
+    """pair_bands of image pairs against the float64 truth: per entry, worst band <= 4 x (the same on torch.fft.rfft2 in float32) + 1e-6"""
+    H, W = shape
+    for name, (a, b) in _pairs(H, W, B, seed=H + W + B).items():
+        mse = float(((a.astype(np.float64) - b) ** 2).mean())
+        for nb in (8, 32) if shape != (2, 2) else BANDS:
+            truth = ref.pair_bands(a, b, nb)
+            f32 = ref.spectrum_sums(torch.fft.rfft2(torch.from_numpy(a)).numpy(), torch.fft.rfft2(torch.from_numpy(b)).numpy(), H, W, nb)
+            got = S.pair_bands(cuda(a), cuda(b), nb).cpu().numpy()
+            assert got.shape == (B, 3, nb + 1, 5)
+            e_got, e_ref = _worst_band_error(got, truth), _worst_band_error(f32, truth)
+            ratio = float((e_got / np.maximum(e_ref, 1e-300)).max()) if e_ref.min() > 0 else float("nan")
+            print(f"{H}x{W} B {B} {name} ({-10 * np.log10(mse):.1f} dB) nb {nb}: worst band error per entry {e_got} (fp32 torch {e_ref}) ratio {ratio:.2f}")
+            WORST["end to end worst-band error / fp32 torch"] = max(WORST.get("end to end worst-band error / fp32 torch", 0.0), np.nan_to_num(ratio))
+            assert (e_got <= 4 * e_ref + 1e-6).all(), (name, nb, e_got, e_ref)
+        m = S.fourier_metrics(cuda(a), cuda(b), 8)
+        want = [ref.metrics(t, H, W) for t in ref.pair_bands(a, b, 8)]
+        for g, w in zip(m, want):
+            assert abs(g["mse"] - w["mse"]) <= 1e-5 * w["mse"] and abs(g["amp_share"] + g["pha_share"] - 1) <= 1e-15
+            assert abs(g["amp_share"] - w["amp_share"]) <= 1e-4 and abs(g["dc_share"] - w["dc_share"]) <= 1e-4
+
+
+def test_same_bits_on_every_call_and_in_every_slot(S):
+    """a second call, and the same pair in slot 0 of B = 1 and in slot 2 of B = 3"""
+    H, W = 96, 160
+    a, b = _pairs(H, W, 3, seed=5)["gain+noise"]
+    ad, bd = cuda(a), cuda(b)
+    first = S.pair_bands(ad, bd, 8)
+    assert torch.equal(first, S.pair_bands(ad, bd, 8))
+    alone = S.pair_bands(ad[2:3].contiguous(), bd[2:3].contiguous(), 8)
+    assert torch.equal(alone[0], first[2])
+    assert S.fourier_metrics(ad[2:3].contiguous(), bd[2:3].contiguous(), 8)[0] == S.fourier_metrics(ad, bd, 8)[2]
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_identical_halved_and_rolled(S, shape):
+    """identical images: total, amplitude, phase and L1 are exactly 0 in every band; b = a / 2 (exact in fp32, and the FFT carries a power of
+    two through exactly): all amplitude, pha_share <= 1e-12; b = roll(a, (3, 5)): all phase, amp_share bounded as the end-to-end test bounds
+    an entry, against the float32 torch.fft figure"""
+    H, W = shape
+    a = _pairs(H, W, 2, seed=H * W)["gain+noise"][1]
+    ad = cuda(a)
+    s = S.pair_bands(ad, ad.clone(), 8).cpu().numpy()
+    assert (s[..., [0, 1, 2, 4]] == 0).all() and (s[..., 3].sum(axis=-1) > 0).all()
+    m = S.fourier_metrics(ad, ad.clone(), 8)[0]
+    assert m["mse"] == 0 and m["psnr"] == m["psnr_amp"] == m["psnr_pha"] == float("inf") and m["fft_l1"] == 0
+
+    for m in S.fourier_metrics(ad, cuda(a * np.float32(0.5)), 8):
+        print(f"{H}x{W} halved: pha_share {m['pha_share']:.3e}")
+        assert m["pha_share"] <= 1e-12 and abs(m["amp_share"] - 1) <= 1e-12
+
+    r = np.ascontiguousarray(np.roll(a, (3, 5), axis=(2, 3)))
+    got = S.fourier_metrics(ad, cuda(r), 8)
+    f32 = ref.spectrum_sums(torch.fft.rfft2(torch.from_numpy(a)).numpy(), torch.fft.rfft2(torch.from_numpy(r)).numpy(), H, W, 8)
+    for m, t in zip(got, f32):
+        bound = 4 * ref.metrics(t, H, W)["amp_share"] + 1e-6
+        print(f"{H}x{W} rolled: amp_share {m['amp_share']:.3e} (bound {bound:.3e})")
+        assert m["amp_share"] <= bound
+
+
+# ---------------------------------------------------------------- 8  the reference's FFTLoss
+def test_fft_l1_against_the_reference(S):
+    """fft_l1 against FFTLoss of the reference as tests/golden/make_golden_fourier.py recorded it (the GPU test reads only the fixture):
+    within the value's stored distance from the float64 formula plus the bound of the end-to-end test on this entry"""
+    z = np.load(os.path.join(GOLDEN, "fourier.npz"))
+    cases = json.loads(bytes(z["cases_json"]).decode())
+    assert sorted(cases) == ["gain_noise", "near_45db", "rolled"]
+    for name, c in cases.items():
+        rs, gt = z[name + "_restored"], z[name + "_gt"]
+        assert c["distance"] <= 1e-5
+        got = S.calculate_fourier(rs, gt, bgr=False)["fft_l1"]
+        a, b = (np.ascontiguousarray(u.transpose(2, 0, 1)).astype(np.float32) / np.float32(255) for u in (rs, gt))
+        exact = ref.fft_l1(a, b)
+        d32 = torch.fft.rfft2(torch.from_numpy(a)) - torch.fft.rfft2(torch.from_numpy(b))
+        f32 = float((d32.real.double().abs() + d32.imag.double().abs()).sum() / (2 * d32.numel()))
+        bound = c["distance"] + 4 * abs(f32 - exact) / exact + 1e-6
+        print(f"{name}: fft_l1 {got!r} reference {c['fft_l1']!r} relative difference {abs(got - c['fft_l1']) / c['fft_l1']:.3e} (bound {bound:.3e})")
+        assert abs(got - c["fft_l1"]) <= bound * c["fft_l1"]
+
+
+# ---------------------------------------------------------------- 9  8-bit images
+def test_calculate_fourier_is_fourier_metrics_on_the_pre_u8_planes(S):
+    """uint8 HWC pairs, single and batched, B, G, R and R, G, B: bit for bit fourier_metrics on the unpadded fdn_pre_u8 planes"""
+    from fdn_hip import ops
+    lib = ops.lib()
+    h, w = 34, 38
+    gt = ref.textured(h, w, 3, n=3)
+    rs = np.clip(gt.astype(np.int64) + np.random.default_rng(4).integers(-9, 10, gt.shape), 0, 255).astype(np.uint8)
+    for bgr in (True, False):
+        planes = []
+        for u in (rs, gt):
+            p = torch.empty((3, 3, h, w), device="cuda:0", dtype=torch.float32)
+            assert lib.fdn_pre_u8(_ptr(cuda(u)), _ptr(p), 3, h, w, h, w, int(bgr), ops.stream()) == 0
+            planes.append(p)
+        want = S.fourier_metrics(planes[0], planes[1], 8)
+        assert S.calculate_fourier(rs, gt, bgr=bgr) == want == S.calculate_fourier(cuda(rs), cuda(gt), bands=8, bgr=bgr)
+        assert S.calculate_fourier(rs[1], gt[1], bgr=bgr) == want[1]
+        rgb = np.ascontiguousarray(rs[..., ::-1] if bgr else rs).transpose(0, 3, 1, 2).astype(np.float32) / np.float32(255)
+        assert np.array_equal(planes[0].cpu().numpy(), rgb)                   # the planes are R, G, B in [0, 1]
+    m = S.calculate_fourier(rs[0], gt[0])
+    mse = ((rs[0].astype(np.float64) - gt[0]) ** 2).mean()
+    assert abs(m["psnr"] - 10 * np.log10(255.0 ** 2 / mse)) <= 1e-4          # the PSNR of the 8-bit pair
+
+
+# ---------------------------------------------------------------- 10  the command lines
+def _run(script, *args):
+    out = subprocess.run([sys.executable, os.path.join(PKG, script), *args], capture_output=True, text=True, timeout=600)
+    print(out.stdout)
+    assert out.returncode == 0, out.stderr
+    return out.stdout
+
+
+FOURIER = r"Amp: (\S+), Pha: (\S+), DC: (\S+), FFT-L1: (\S+)"
+TOOL_LINE = re.compile(r"^ *(\d+): (\S+) *\. \tPSNR: (\S+) dB, \t" + FOURIER + "$", re.M)
+TOOL_AVERAGE = re.compile(r"^Average: PSNR: (\S+) dB, " + FOURIER + "$", re.M)
+PLAIN_LINE = re.compile(r"^ *(\d+): (\S+) *\. \tPSNR: (\S+) dB, \tSSIM: (\S+)$", re.M)
+VAL_LINE = re.compile(r"^ *(\d+): (\S+) *\. \tPSNR: (\S+) dB, \tSSIM: (\S+), \t" + FOURIER + "$", re.M)
+VAL_AVERAGE = re.compile(r"^Average: PSNR: (\S+) dB, SSIM: (\S+), " + FOURIER + "$", re.M)
+KEYS = ("amp_share", "pha_share", "dc_share", "fft_l1")
+
+
+def _check_csv_rows(S, lines, first_cols, want, bands):
+    assert lines[0].split(",")[first_cols:] == S.csv_header(bands) and len(lines) == 1 + len(want)
+    for line, m in zip(lines[1:], want):
+        cells = line.split(",")[first_cols:]
+        assert cells == S.csv_row(m) and len(cells) == 8 + 4 * (bands + 1)
+
+
+def test_command_lines(S, tmp_path):
+    """calculate_fourier_metrics.py and validate_fdn.py --fourier on a few small PNGs, in child processes: the printed lines, the averages
+    and the csv columns are the Python API's; without the flag validate_fdn.py prints and writes what it did before"""
+    from PIL import Image
+    from basicsr.models.archs.FDN_arch import FDN
+    from fdn_hip import harness
+    gt = ref.textured(40, 72, 21, n=3)
+    lq = (gt * 0.3).astype(np.uint8)
+    rs = np.clip(np.rint(gt * 0.9 + np.random.default_rng(22).normal(0, 6, gt.shape)), 0, 255).astype(np.uint8)
+    small = ref.textured(24, 40, 23, n=2)                                                            # a pair of another size: its own batch
+    for d in ("lq", "gt", "rs"):
+        (tmp_path / d).mkdir()
+    for i in range(3):
+        Image.fromarray(lq[i]).save(tmp_path / "lq" / f"f{i}.png")
+        Image.fromarray(gt[i]).save(tmp_path / "gt" / f"f{i}.png")
+        Image.fromarray(rs[i]).save(tmp_path / "rs" / f"f{i}_FDN.png")
+    Image.fromarray(small[0]).save(tmp_path / "gt" / "f3.png")
+    Image.fromarray(small[1]).save(tmp_path / "rs" / "f3_FDN.png")
+
+    text = _run("calculate_fourier_metrics.py", "--gt", str(tmp_path / "gt" / "*.png"), "--restored", str(tmp_path / "rs" / "*.png"), "--batch", "2",
+                "--bands", "4", "--csv", str(tmp_path / "fourier.csv"))
+    want = S.calculate_fourier(rs, gt, bands=4, bgr=False) + [S.calculate_fourier(small[1], small[0], bands=4, bgr=False)]
+    rows = TOOL_LINE.findall(text)
+    assert [r[1] for r in rows] == ["f0", "f1", "f2", "f3"]
+    for r, m in zip(rows, want):
+        assert r[2:] == (f"{m['psnr']:.6f}",) + tuple(f"{m[k]:.6f}" for k in KEYS)
+    avg = {k: sum(m[k] for m in want) / 4 for k in ("psnr",) + KEYS}
+    assert TOOL_AVERAGE.search(text).groups() == (f"{avg['psnr']:.6f}",) + tuple(f"{avg[k]:.6f}" for k in KEYS)
+    lines = (tmp_path / "fourier.csv").read_text().splitlines()
+    assert lines[0].startswith("gt,restored,mse,psnr,amp_share,") and lines[1].split(",")[0].endswith("f0.png")
+    _check_csv_rows(S, lines, 2, want, 4)
+
+    torch.save({"params": fdn_weights(tame=0.03)}, tmp_path / "fdn.pth")
+    common = ["--fdn", str(tmp_path / "fdn.pth"), "--lq", str(tmp_path / "lq" / "*.png"), "--gt", str(tmp_path / "gt" / "f[012].png"), "--batch", "2"]
+    plain = _run("validate_fdn.py", *common, "--csv", str(tmp_path / "plain.csv"))
+    text = _run("validate_fdn.py", *common, "--csv", str(tmp_path / "four.csv"), "--fourier", "--fourier-bands", "4")
+    net = FDN()
+    net.load_state_dict(fdn_weights(tame=0.03), strict=True)
+    net = net.to("cuda:0").eval()
+    out, psnr, ssim, ratio = harness.validate_u8(net, None, cuda(lq), cuda(gt), ratio_mode="gt", bgr=False)
+    want = S.calculate_fourier(out, cuda(gt), bands=4, bgr=False)
+    # without the flag: the lines and the csv of before
+    assert [(r[1], r[2], r[3]) for r in PLAIN_LINE.findall(plain)] == [(f"f{i}", f"{psnr[i]:.6f}", f"{ssim[i]:.6f}") for i in range(3)]
+    assert f"Average: PSNR: {sum(psnr) / 3:.6f} dB, SSIM: {sum(ssim) / 3:.6f}\n" in plain and "Amp:" not in plain
+    paths = [str(tmp_path / "lq" / f"f{i}.png") for i in range(3)]
+    assert (tmp_path / "plain.csv").read_text() == "frame,psnr,ssim,ratio\n" + "".join(
+        f"{paths[i]},{psnr[i]!r},{ssim[i]!r},{ratio[i, 0].item()!r}\n" for i in range(3))
+    # with it: the same figures, then the Fourier ones
+    rows = VAL_LINE.findall(text)
+    assert [r[1:4] for r in rows] == [(f"f{i}", f"{psnr[i]:.6f}", f"{ssim[i]:.6f}") for i in range(3)]
+    for r, m in zip(rows, want):
+        assert r[4:] == tuple(f"{m[k]:.6f}" for k in KEYS)
+    assert VAL_AVERAGE.search(text).groups() == (f"{sum(psnr) / 3:.6f}", f"{sum(ssim) / 3:.6f}") + tuple(f"{sum(m[k] for m in want) / 3:.6f}" for k in KEYS)
+    lines = (tmp_path / "four.csv").read_text().splitlines()
+    assert lines[0].startswith("frame,psnr,ssim,ratio,mse,psnr,amp_share,")
+    assert [ln.split(",")[:4] for ln in lines[1:]] == [ln.split(",") for ln in (tmp_path / "plain.csv").read_text().splitlines()[1:]]
+    _check_csv_rows(S, lines, 4, want, 4)
