@@ -1247,8 +1247,10 @@ int launch_generic(const conv1x1_route& r, const fdn_conv1x1_desc& d, hipStream_
     if constexpr (generic_nw4(MT, PRO)) {
         if (r.nw == 4) return launch<MT, PRO, 4, false>(r, d, s);
     }
-    // (the 8-wave copy exists for every (MT, PRO), also where the route always answers 4: the object keeps the set of kernels it had)
-    if (r.nw == 8) return generic_nw4(MT, PRO) ? FDN_ERR_LAUNCH : launch<MT, PRO, 8, false>(r, d, s);
+    // (no 8-wave copy where the route always answers 4: such a kernel had device code and no launcher - tests/kernel_table.txt)
+    if constexpr (!generic_nw4(MT, PRO)) {
+        if (r.nw == 8) return launch<MT, PRO, 8, false>(r, d, s);
+    }
     return FDN_ERR_LAUNCH;
 }
 template <int MT>

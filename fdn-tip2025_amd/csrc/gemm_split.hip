@@ -677,16 +677,18 @@ int launch_strip(const conv1x1_route& r, const fdn_conv1x1_desc& d, hipStream_t 
     a.total_ptiles = d.B * a.tiles_per_img;
     a.ntiles = 1;
     if constexpr (strip2_nks(NKS)) {
-        if (r.strip2) {
-            fdn_note_bf16_launch();
-            hipLaunchKernelGGL((gemm_split_strip2_kernel<NKS, PRO>), dim3((unsigned)a.total_ptiles), dim3(256), 0, s, a, (unsigned)split_pack_bytes(d.N, d.K, 0));
-            return fdn_launch_status();
-        }
+        // the route answers strip2 for every descriptor of these NKS: N <= STRIP_MAX_N keeps the packed weights (under 1 MB) far below the 2 GB of
+        // one descriptor, the only condition that would take strip2 away - so the plain strip kernel is not built for them
+        if (!r.strip2) return FDN_ERR_LAUNCH;
+        fdn_note_bf16_launch();
+        hipLaunchKernelGGL((gemm_split_strip2_kernel<NKS, PRO>), dim3((unsigned)a.total_ptiles), dim3(256), 0, s, a, (unsigned)split_pack_bytes(d.N, d.K, 0));
+        return fdn_launch_status();
+    } else {
+        if (r.strip2) return FDN_ERR_LAUNCH;
+        fdn_note_bf16_launch();
+        hipLaunchKernelGGL((gemm_split_strip_kernel<NKS, PRO>), dim3((unsigned)a.total_ptiles), dim3(256), 0, s, a);
+        return fdn_launch_status();
     }
-    if (r.strip2) return FDN_ERR_LAUNCH;
-    fdn_note_bf16_launch();
-    hipLaunchKernelGGL((gemm_split_strip_kernel<NKS, PRO>), dim3((unsigned)a.total_ptiles), dim3(256), 0, s, a);
-    return fdn_launch_status();
 }
 
 // fdn_fcaffn_in_pack: the two folded image maps as MFMA A operands: cell (map, k-step, part, 32-channel tile, lane) holds the part-th

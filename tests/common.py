@@ -380,6 +380,7 @@ CONV1X1_SPLIT_ROUTES = {
     (128, 128, 184, 320, 'muladd', 'muladd'): 'split<muladd>',
     (96, 460, 9, 13, 'ln', 'none'): 'split_strip<6,ln,strip2=0>',
     (100, 300, 9, 13, 'none', 'bias'): 'split_strip<7,none,strip2=0>',
+    (100, 300, 9, 13, 'ln', 'none'): 'split_strip<7,ln,strip2=0>',
     (128, 612, 184, 320, 'ln', 'bias'): 'split_strip<8,ln,strip2=1>',
     (32, 86, 23, 40, 'ln', 'none'): 'split_strip<2,ln,strip2=0>',
     (64, 172, 46, 80, 'ln', 'none'): 'split_strip<4,ln,strip2=0>',

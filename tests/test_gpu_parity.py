@@ -393,7 +393,7 @@ def test_conv1x1_variants(A, K, N, H, W, pro):
 @pytest.mark.parametrize("K,N,H,W,pro,epi", [(128, 612, 23, 40, "ln", "none"), (128, 345, 184, 320, "ln", "none"), (459, 128, 23, 41, "ln3", "res"),
                                             (345, 128, 184, 320, "none", "res"), (128, 128, 23, 40, "muladd", "muladd"), (96, 96, 5, 7, "none", "bias"),
                                             (100, 130, 9, 13, "ln", "res"), (345, 128, 8, 17, "ln3", "none"), (128, 128, 184, 320, "muladd", "muladd"),
-                                            (96, 460, 9, 13, "ln", "none"), (100, 300, 9, 13, "none", "bias"), (128, 612, 184, 320, "ln", "bias"),
+                                            (96, 460, 9, 13, "ln", "none"), (100, 300, 9, 13, "none", "bias"), (100, 300, 9, 13, "ln", "none"), (128, 612, 184, 320, "ln", "bias"),
                                             (32, 86, 23, 40, "ln", "none"), (64, 172, 46, 80, "ln", "none"), (48, 129, 9, 13, "ln", "bias"),
                                             (24, 64, 9, 13, "none", "none"), (64, 172, 368, 640, "ln", "none")])
 def test_conv1x1_split_bf16_kernel(A, K, N, H, W, pro, epi):
@@ -563,11 +563,13 @@ def test_gemm_takes_its_own_layernorm_statistics(A, K, N, H, W, pro):
     assert torch.equal(own, ops.conv1x1(xs, dev(w), res=dev(r), cache=(wc, "t"), **mk(None)))
 
 
-@pytest.mark.parametrize("C,N,H,W", [(86, 32, 24, 40), (345, 128, 16, 24), (64, 64, 46, 40), (43, 16, 8, 35), (172, 64, 40, 72),
+@pytest.mark.parametrize("C,N,H,W", [(86, 32, 24, 40), (345, 128, 16, 24), (64, 64, 46, 40), (43, 16, 8, 35), (43, 16, 16, 40), (45, 80, 13, 35), (172, 64, 40, 72),
                                      (129, 48, 16, 136), (32, 32, 736, 1280)])
 def test_ffn_tail_fused_equals_reference(A, C, N, H, W):
     """fdn_ffn_tail (gate + project_out + residual + statistics in one launch, both kernel forms) against fp64: odd widths,
-    odd channel counts (the gate branch of a pair then reads two different planes), partial 64-column tiles, bf16-storage input."""
+    odd channel counts (the gate branch of a pair then reads two different planes), partial 64-column tiles, bf16-storage input.
+    (43, 16, 16, 40) is the odd channel count on the sliding-window form at N <= 32 (ffn_tail_sw_kernel<1, 4, ., true>): W % 4 == 0, two
+    8-row tiles, a partial 64-column tile; (45, 80, 13, 35) is the three-tile output of the chunked form (ffn_tail_kernel<3>, 64 < N <= 96)."""
     import ctypes
     import fdn_hip
     from fdn_hip import ops
@@ -601,9 +603,10 @@ def test_ffn_tail_fused_equals_reference(A, C, N, H, W):
 
 @pytest.mark.parametrize("Cin,Cout,H,W,stride", [(64, 32, 24, 40, 1), (3, 32, 16, 35, 1), (12, 12, 9, 21, 1), (32, 3, 16, 24, 1),
                                                  (128, 64, 8, 16, 1), (64, 128, 8, 24, 1), (12, 24, 18, 22, 2), (24, 48, 9, 21, 2),
-                                                 (5, 7, 11, 13, 2)])
+                                                 (5, 7, 11, 13, 2), (116, 24, 9, 21, 1)])
 def test_conv3x3_paths(A, Cin, Cout, H, W, stride):
-    """LDS-weight direct kernel (Cout <= 64, stride 1 and 2), MFMA implicit GEMM (wider / slice too big for LDS)."""
+    """LDS-weight direct kernel (Cout <= 64, stride 1 and 2), MFMA implicit GEMM (wider / slice too big for LDS; 116 -> 24: a 16-channel
+    weight slice of 116 x 9 taps is past the direct kernel's 64 KB and 116 % 8 != 0, so the one-tile fp32-MFMA form conv3x3_kernel<1, 4> runs)."""
     from fdn_hip import ops
     x, w, b = _rnd(2, Cin, H, W, seed=1), _rnd(Cout, Cin, 3, 3, seed=2) / (3 * Cin ** 0.5), _rnd(Cout, seed=3)
     ref = torch.nn.functional.conv2d(x.double(), w.double(), b.double(), padding=1, stride=stride)
@@ -640,10 +643,14 @@ def test_conv3x3_tiled_options(A, Cin, Cout, H, W, act, res_before):
 
 @pytest.mark.parametrize("Cin,Cout,H,W", [(24, 12, 9, 13), (48, 24, 8, 16), (6, 5, 7, 9), (24, 12, 46, 80), (24, 20, 5, 77), (48, 24, 23, 40)])
 def test_conv_transpose4x4s2(A, Cin, Cout, H, W):
+    import fdn_hip
     from fdn_hip import ops
     x, w, b = _rnd(2, Cin, H, W, seed=1), _rnd(Cin, Cout, 4, 4, seed=2) / (4 * Cin ** 0.5), _rnd(Cout, seed=3)
     ref = torch.nn.functional.conv_transpose2d(x.double(), w.double(), b.double(), stride=2, padding=1)
     assert rel_rms(ops.conv_transpose4x4s2(dev(x), dev(w), dev(b), 0).cpu(), ref) < 2e-6
+    # the activation is a run-time branch of the one kernel: MAR's f2_up / f3_up run LeakyReLU(0.1) (FDN_arch.py BasicConv, relu=True)
+    leaky = torch.nn.functional.leaky_relu(ref, 0.1)
+    assert rel_rms(ops.conv_transpose4x4s2(dev(x), dev(w), dev(b), fdn_hip.ACT_LEAKY).cpu(), leaky) < 2e-6
 
 
 def test_fdsa_out_level1_equals_fallback(A):

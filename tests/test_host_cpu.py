@@ -585,7 +585,7 @@ def test_conv1x1_route_pins_the_network_shapes(lib):
 
 
 def test_conv1x1_route_pins_the_cases_of_the_gpu_tests(lib):
-    """Each conv1x1 case of tests/test_gpu_geometry.py and tests/test_gpu_parity.py still reaches the kernel it was chosen for (the GPU tests
+    """Each conv1x1 case of tests/test_gpu_geometry.py, tests/test_gpu_kernel_forms.py and tests/test_gpu_parity.py still reaches the kernel it was chosen for (the GPU tests
     assert the same on the descriptor they really pass)."""
     import importlib
     from common import (CONV1X1_GEOMETRY_ROUTES, CONV1X1_SPLIT_ROUTES, CONV1X1_TWO_INPUT_ROUTES, CONV1X1_VARIANT_ROUTES, conv1x1_fields,
@@ -604,6 +604,10 @@ def test_conv1x1_route_pins_the_cases_of_the_gpu_tests(lib):
         assert _route_name(conv1x1_fields(K, N, H * W, pro, epi, so=int(N <= 128 and K >= 96), wpk=1)) == want, (K, N, pro, epi)
     for (K0, K1, N, H, W), want in CONV1X1_TWO_INPUT_ROUTES.items():
         assert _route_name(conv1x1_fields(K0 + K1, N, H * W, segs=(K0, K1), so=int(N <= 128), wpk=1, B=2 if H < 100 else 1)) == want, (K0, K1, N)
+    forms = importlib.import_module("test_gpu_kernel_forms").CONV1X1
+    for name, (K, N, H, W, pro, epi, act, want_stats, xbf, want) in forms.items():
+        assert _route_name(conv1x1_fields(K, N, H * W, pro, epi, act=act, so=int(want_stats), xbf=xbf)) == want, name
+    assert len({c[-1] for c in forms.values()}) == len(forms)                                            # no two cases on one instantiation
 
 
 def test_conv1x1_route_argument_validation(lib):
