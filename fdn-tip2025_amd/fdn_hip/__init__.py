@@ -1,5 +1,5 @@
 """ctypes binding of libfdn_hip.so (the C ABI declared in include/fdn_hip.h, include/fdn_video.h, include/fdn_temporal.h,
-include/fdn_vmetrics.h, include/fdn_ensemble.h and include/fdn_spectral.h).
+include/fdn_vmetrics.h, include/fdn_ensemble.h, include/fdn_spectral.h and include/fdn_lowlight.h).
 
 PyTorch is plumbing here: it owns device memory and the current HIP stream; every compute step
 of the FDN path is a call into the library.  There is NO CPU or eager fallback: if the shared
@@ -44,6 +44,7 @@ TEMPORAL_ABI_VERSION = 1  # include/fdn_temporal.h (the ratio filter across fram
 VMETRICS_ABI_VERSION = 1  # include/fdn_vmetrics.h (video evaluation from codec samples), likewise
 ENSEMBLE_ABI_VERSION = 1  # include/fdn_ensemble.h (the flipped and transposed copies of the self-ensemble), likewise
 SPECTRAL_ABI_VERSION = 1  # include/fdn_spectral.h (Fourier evaluation: the complex spectrum, the error per band in amplitude and phase), likewise
+LOWLIGHT_ABI_VERSION = 1  # include/fdn_lowlight.h (low-light evaluation: lightness order error, CIEDE2000), likewise
 
 
 def lib_path():
@@ -84,6 +85,10 @@ def lib():
             v = _lib.fdn_spectral_abi_version()
             _lib = None
             raise ImportError(f"{_LIB_PATH} has spectral ABI version {v}, this binding needs {SPECTRAL_ABI_VERSION}: rebuild with build.sh")
+        if _lib.fdn_lowlight_abi_version() != LOWLIGHT_ABI_VERSION:
+            v = _lib.fdn_lowlight_abi_version()
+            _lib = None
+            raise ImportError(f"{_LIB_PATH} has lowlight ABI version {v}, this binding needs {LOWLIGHT_ABI_VERSION}: rebuild with build.sh")
     return _lib
 
 
@@ -96,8 +101,10 @@ def _declare(l, missing_ok=False):
     from ._abi_vmetrics import PROTOTYPES as VMETRICS_PROTOTYPES
     from ._abi_ensemble import PROTOTYPES as ENSEMBLE_PROTOTYPES
     from ._abi_spectral import PROTOTYPES as SPECTRAL_PROTOTYPES
+    from ._abi_lowlight import PROTOTYPES as LOWLIGHT_PROTOTYPES
     kinds = {"P": ctypes.c_void_p, "I": ctypes.c_int, "L": ctypes.c_long, "F": ctypes.c_float, "DESC": ctypes.POINTER(Conv1x1Desc)}
-    tables = (PROTOTYPES, VIDEO_PROTOTYPES, TEMPORAL_PROTOTYPES, VMETRICS_PROTOTYPES, ENSEMBLE_PROTOTYPES, SPECTRAL_PROTOTYPES)
+    tables = (PROTOTYPES, VIDEO_PROTOTYPES, TEMPORAL_PROTOTYPES, VMETRICS_PROTOTYPES, ENSEMBLE_PROTOTYPES, SPECTRAL_PROTOTYPES,
+              LOWLIGHT_PROTOTYPES)
     for name, (ret, sig) in [item for t in tables for item in t.items()]:
         f = getattr(l, name, None) if missing_ok else getattr(l, name)      # AttributeError: the library lacks a symbol the header declares
         if f is None:

@@ -115,8 +115,8 @@ def ssim3d_channel_matrix():
     return m
 
 
-def _u8_pair(img1, img2, crop_border):
-    """-> (a, b, single): two contiguous uint8 [B][h][w][3] tensors on one ROCm device"""
+def _u8_pair(img1, img2, crop_border, what="calculate_psnr_ssim_u8"):
+    """-> (a, b, single): two contiguous uint8 [B][h][w][3] tensors on one ROCm device; `what` names the caller in the errors"""
     s1, s2 = tuple(getattr(img1, "shape", ())), tuple(getattr(img2, "shape", ()))
     if s1 != s2:
         raise FdnHipError(f"Image shapes are different: {s1}, {s2}.")                                # psnr_ssim.py:30
@@ -125,7 +125,7 @@ def _u8_pair(img1, img2, crop_border):
         if isinstance(img, np.ndarray):
             img = torch.from_numpy(np.ascontiguousarray(img))
         if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or img.dim() not in (3, 4) or img.shape[-1] != 3:
-            raise FdnHipError("calculate_psnr_ssim_u8 takes uint8 images (h,w,3) or (B,h,w,3), numpy arrays or tensors, got "
+            raise FdnHipError(f"{what} takes uint8 images (h,w,3) or (B,h,w,3), numpy arrays or tensors, got "
                               f"{getattr(img, 'dtype', type(img).__name__)} {tuple(getattr(img, 'shape', ()))}")
         out.append(img if img.dim() == 4 else img.unsqueeze(0))
     cb = int(crop_border)
@@ -133,14 +133,14 @@ def _u8_pair(img1, img2, crop_border):
     if cb < 0:
         raise FdnHipError("crop_border must be >= 0")
     if B < 1 or h <= 2 * cb or w <= 2 * cb:
-        raise FdnHipError(f"calculate_psnr_ssim_u8: nothing is left of {B} image(s) of {h}x{w} with crop_border={cb}")
+        raise FdnHipError(f"{what}: nothing is left of {B} image(s) of {h}x{w} with crop_border={cb}")
     devs = {t.device for t in out if t.is_cuda}
     if len(devs) > 1:
-        raise FdnHipError(f"calculate_psnr_ssim_u8: the two images are on different devices ({out[0].device}, {out[1].device})")
+        raise FdnHipError(f"{what}: the two images are on different devices ({out[0].device}, {out[1].device})")
     dev = next(iter(devs), None)
     if dev is None:
         if not torch.cuda.is_available():
-            raise FdnHipError("calculate_psnr_ssim_u8 needs a ROCm device; there is no CPU fallback")
+            raise FdnHipError(f"{what} needs a ROCm device; there is no CPU fallback")
         dev = torch.device("cuda", torch.cuda.current_device())
     return out[0].to(dev).contiguous(), out[1].to(dev).contiguous(), len(s1) == 3
 

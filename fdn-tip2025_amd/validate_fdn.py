@@ -18,7 +18,10 @@ tiles with ramps across their overlaps instead of the reference's average (not w
 geometric self-ensemble (fdn_hip.ensemble; not what the reference scores either): FDN on that many flipped / transposed copies of every
 frame or tile, all fed the ratio of the untransformed one, averaged.  --fourier appends the Fourier figures of fdn_hip.spectral to every
 line and to the csv (calculate_fourier_metrics.py has what they mean): the amplitude, phase and zero-frequency share of the MSE of the whole
-8-bit frame (no crop_border; the width must be even), the reference's FFTLoss, and per band the columns of that tool's csv.
+8-bit frame (no crop_border; the width must be even), the reference's FFTLoss, and per band the columns of that tool's csv.  --lowlight appends the two low-light scores of fdn_hip.lowlight
+(calculate_lowlight_metrics.py has what they mean): loe, the lightness order error of the input frame against the restored one on a grid of
+--loe-size points along the short side (0: every pixel), and deltae, the mean CIEDE2000 difference of the restored frame against the
+ground truth, both from the whole 8-bit frames the driver holds on the GPU anyway.
 """
 import argparse
 import glob
@@ -70,9 +73,17 @@ def parse_args(argv=None):
     add_ensemble_arg(ap)
     ap.add_argument("--fourier", action="store_true", help="also split every frame's error into amplitude and phase per frequency band")
     ap.add_argument("--fourier-bands", type=int, default=8, help="radial frequency bands besides the zero-frequency bin (1 .. 32)")
+    # absent unless given, so that the namespace of a command line without them is what it was
+    ap.add_argument("--lowlight", action="store_true", default=argparse.SUPPRESS,
+                    help="also score the lightness order error against the input and the CIEDE2000 difference against the ground truth")
+    ap.add_argument("--loe-size", type=int, default=argparse.SUPPRESS, help="with --lowlight: points along the short side of LOE's sample grid (default 50; 0 = full resolution)")
     a = ap.parse_args(argv)
     if not 1 <= a.fourier_bands <= 32:
         ap.error("--fourier-bands must be in 1 .. 32")
+    if hasattr(a, "loe_size") and not hasattr(a, "lowlight"):
+        ap.error("--loe-size needs --lowlight")
+    if getattr(a, "loe_size", 0) < 0:
+        ap.error("--loe-size must be >= 0")
     if a.ratio == "lpnet" and not a.lpnet:
         ap.error("--ratio lpnet needs --lpnet")
     if a.crop_border < 0:
@@ -100,6 +111,11 @@ def main(argv=None):
         from calculate_fourier_metrics import SUMMARY_KEYS, fourier_line, mean_of
         from fdn_hip import FdnHipError, spectral
 
+    want_ll, loe_size = getattr(a, "lowlight", False), getattr(a, "loe_size", 50)
+    if want_ll:
+        from calculate_lowlight_metrics import lowlight_line
+        from fdn_hip import FdnHipError, lowlight
+
     dev = torch.device(a.device)
     torch.cuda.set_device(dev)
     net = Net().to(dev).eval()
@@ -111,7 +127,7 @@ def main(argv=None):
     mode = RATIO_MODE[(a.ratio, a.variant)]
 
     n = len(a.pairs)
-    psnr, ssim, ratio, fourier = [None] * n, [None] * n, [None] * n, [None] * n
+    psnr, ssim, ratio, fourier, ll = [None] * n, [None] * n, [None] * n, [None] * n, [None] * n
     with ThreadPoolExecutor(max_workers=4) as pool:
         writers = []
         for idx, lqs, gts in decoded_groups(a.pairs, a.batch, pool):
@@ -128,10 +144,17 @@ def main(argv=None):
                     fm = spectral.calculate_fourier(out, gt, bands=a.fourier_bands, bgr=False)
                 except FdnHipError as e:
                     sys.exit(f"validate_fdn.py: --fourier: {e}")
+            if want_ll:
+                try:
+                    lm = lowlight.lowlight_metrics(lq, out, gt, size=loe_size, bgr=False)
+                except FdnHipError as e:
+                    sys.exit(f"validate_fdn.py: --lowlight: {e}")
             for k, i in enumerate(idx):
                 psnr[i], ssim[i], ratio[i] = p[k], s[k], r[k]
                 if a.fourier:
                     fourier[i] = fm[k]
+                if want_ll:
+                    ll[i] = lm[k]
                 if a.dest:
                     writers.append(pool.submit(write_rgb, a.dest[i], frames[k]))
         for w in writers:
@@ -139,15 +162,18 @@ def main(argv=None):
     for i, (lq_path, _) in enumerate(a.pairs):
         basename = os.path.splitext(os.path.basename(lq_path))[0]
         tail = f", \t{fourier_line(fourier[i])}" if a.fourier else ""
+        tail += f", \t{lowlight_line(ll[i])}" if want_ll else ""
         print(f'{i+1:3d}: {basename:25}. \tPSNR: {psnr[i]:.6f} dB, \tSSIM: {ssim[i]:.6f}{tail}')
     tail = ", " + fourier_line({k: mean_of([m[k] for m in fourier]) for k in SUMMARY_KEYS}) if a.fourier else ""
+    tail += ", " + lowlight_line({k: sum(m[k] for m in ll) / n for k in ("loe", "deltae")}) if want_ll else ""
     print(f'Average: PSNR: {sum(psnr) / n:.6f} dB, SSIM: {sum(ssim) / n:.6f}{tail}')
     if a.csv:
         os.makedirs(os.path.dirname(a.csv) or ".", exist_ok=True)
         with open(a.csv, "w") as f:
-            f.write("frame,psnr,ssim,ratio" + ("," + ",".join(spectral.csv_header(a.fourier_bands)) if a.fourier else "") + "\n")
+            f.write("frame,psnr,ssim,ratio" + ("," + ",".join(spectral.csv_header(a.fourier_bands)) if a.fourier else "") + (",loe,deltae" if want_ll else "") + "\n")
             for i, ((lq_path, _), p, s, r) in enumerate(zip(a.pairs, psnr, ssim, ratio)):
                 tail = "," + ",".join(spectral.csv_row(fourier[i])) if a.fourier else ""
+                tail += f",{ll[i]['loe']!r},{ll[i]['deltae']!r}" if want_ll else ""
                 f.write(f"{lq_path},{p!r},{s!r},{';'.join(repr(v) for v in r)}{tail}\n")
     if a.dest:
         print(f"{n} frames -> {a.output}")

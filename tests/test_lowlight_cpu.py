@@ -1,0 +1,276 @@
+"""CPU: the host side of the low-light evaluation - the restatement of tests/lowlight_ref.py judged on its own (the histogram identity
+against the brute-force pair count, CIEDE2000 against the published pairs of Sharma, Wu and Dalal), the entry points of
+include/fdn_lowlight.h (version, prototype table, argument checks before any launch, the sample grid and the workspace sizes, which
+are host arithmetic), what fdn_hip.lowlight refuses, and the argument parsing of calculate_lowlight_metrics.py and
+validate_fdn.py --lowlight.  No GPU compute."""
+import ctypes
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import __graft_entry__ as entry  # noqa: F401  (puts the package on sys.path)
+import lowlight_ref as ref
+from fdn_hip import lowlight  # noqa: E402  (the module under test: without it nothing here has a subject)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ["fdn_lowlight_abi_version", "fdn_loe_sample_dims", "fdn_loe_ws", "fdn_loe_u8", "fdn_loe_map_u8", "fdn_deltae00_ws",
+         "fdn_deltae00_u8"]
+# (h, w, size) and the brute-force pair count with ref.dark_pair(h, w, 0)'s stream of random numbers, taken one shape after the other
+IDENTITY = [((37, 53, 0), 391847), ((64, 90, 50), 1264055), ((120, 67, 50), 2054983), ((51, 50, 50), 679588), ((16, 16, 50), 6627)]
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import fdn_hip
+    if not os.path.isfile(fdn_hip.lib_path()):
+        entry.build()
+    return fdn_hip.lib()
+
+
+def test_histogram_identity_is_the_pair_count():
+    """sum J (R + K - 2 C) equals the count over all pairs of samples at the five shapes; the counts are the recorded ones"""
+    g = np.random.default_rng(0)
+    for (h, w, size), count in IDENTITY:
+        a = g.integers(0, 40, (h, w, 3), dtype=np.uint8)
+        b = np.clip(a.astype(int) * 5 + g.integers(-20, 20, (h, w, 3)), 0, 255).astype(np.uint8)
+        brute, hist = ref.loe_brute(a, b, size), ref.loe_hist(a, b, size)
+        assert brute == hist, (h, w, size)
+        assert brute[0] == count and brute[1] == np.prod(ref.sample_dims(h, w, size)), (h, w, size, brute)
+        rd = ref.loe_map(a, b, size)
+        assert rd.shape == ref.sample_dims(h, w, size) and int(rd.sum()) == brute[0]
+    # full lightness range, ties and the two ends of the prefix sums
+    a, b = g.integers(0, 256, (24, 31, 3), dtype=np.uint8), g.integers(0, 256, (24, 31, 3), dtype=np.uint8)
+    a[0, 0], b[0, 0], a[1, 1], b[1, 1] = 0, 255, 255, 0
+    assert ref.loe_brute(a, b, 0) == ref.loe_hist(a, b, 0)
+    assert ref.loe_hist(a, a, 0)[0] == 0
+    assert ref.loe_hist(np.full_like(a, 7), b, 0) == ref.loe_brute(np.full_like(a, 7), b, 0)
+
+
+SHAPES = [(37, 53), (64, 90), (120, 67), (51, 50), (50, 51), (16, 16), (1, 1), (1, 400), (720, 1280), (1080, 1920), (46340, 46340)]
+
+
+def test_sample_rule(lib):
+    """fdn_loe_sample_dims against the restated rule; the rule's indices are in range, increase, and are symmetric about the middle"""
+    for h, w in SHAPES:
+        for size in (0, 1, 2, 49, 50, 51, 100, 719, 720, 2 ** 31 - 1):
+            md, nd = lowlight.sample_dims(h, w, size)
+            assert (md, nd) == ref.sample_dims(h, w, size), (h, w, size)
+            assert 1 <= md <= h and 1 <= nd <= w
+            if size and min(h, w) > size:
+                assert min(md, nd) == size
+                s = min(h, w)
+                assert abs(md - h * size / s) <= 0.5 and abs(nd - w * size / s) <= 0.5         # rounded half up
+            else:
+                assert (md, nd) == (h, w)
+            for n, k in ((h, md), (w, nd)):
+                if n <= 4096:
+                    idx = ref.sample_idx(n, k)
+                    assert idx[0] >= 0 and idx[-1] < n and (np.diff(idx) > 0).all()
+                    assert (idx == np.floor((np.arange(k) + 0.5) * n / k)).all()
+                    if k == n:
+                        assert (idx == np.arange(n)).all()
+    assert lowlight.sample_dims(64, 90, 50) == (50, 70) and lowlight.sample_dims(120, 67, 50) == (90, 50)
+    assert lowlight.sample_dims(45, 30, 20) == (30, 20) and lowlight.sample_dims(5, 3, 2) == (3, 2)       # 3.33 -> 3; 30.0; a half goes up:
+    assert lowlight.sample_dims(7, 4, 2) == (4, 2)                                                          # 3.5 -> 4
+
+
+SHARMA = [((50.0, 2.6772, -79.7751), 2.0425), ((50.0, 3.1571, -77.2803), 2.8615), ((50.0, 2.8361, -74.0200), 3.4412)]
+
+
+def test_ciede2000_restatement():
+    """the three published pairs to four decimals, in float64 and in longdouble; symmetry; 0 for equal colours; CIELAB of white and black"""
+    q = np.array([50.0, 0.0, -82.7485])
+    for ft in (np.float64, np.longdouble):
+        got = [float(ref.de00(np.array(p), q, ft)) for p, _ in SHARMA]
+        assert [round(v, 4) for v in got] == [e for _, e in SHARMA], got
+        assert [round(v, 5) for v in got] == [2.04246, 2.86151, 3.44119]
+    g = np.random.default_rng(3)
+    a, b = g.integers(0, 256, (40, 40, 3), dtype=np.uint8), g.integers(0, 256, (40, 40, 3), dtype=np.uint8)
+    d = ref.deltae_u8(a, b)
+    assert d.dtype == np.float64 and np.abs(d - ref.deltae_u8(b, a)).max() <= 1e-12 and (d > 0).all() and d.max() < 130
+    assert (ref.deltae_u8(a, a) == 0).all()
+    assert ref.deltae_u8(a, b, np.longdouble).dtype == np.longdouble
+    assert np.abs(d - ref.deltae_u8(a, b, np.longdouble)).max() < 1e-12
+    white, black = ref.lab(np.array([255, 255, 255], np.uint8)), ref.lab(np.array([0, 0, 0], np.uint8))
+    assert abs(white[0] - 100) < 1e-5 and np.abs(white[1:]).max() < 1e-3 and (black == 0).all()        # the matrix rows sum to the white point to 7 digits
+    assert abs(float(ref.deltae_u8(np.array([0, 0, 0], np.uint8), np.array([255, 255, 255], np.uint8))) - 100) < 1e-5
+
+
+def test_version_and_prototype_table(lib):
+    """the new header has its own version and table; fdn_hip.h stands at ABI 22 with 74 entry points; no name is shared"""
+    import fdn_hip
+    from fdn_hip import _abi, _abi_ensemble, _abi_lowlight, _abi_spectral, _abi_temporal, _abi_video, _abi_vmetrics
+    assert lib.fdn_lowlight_abi_version() == fdn_hip.LOWLIGHT_ABI_VERSION == 1
+    assert lib.fdn_abi_version() == fdn_hip.ABI_VERSION == 22 and len(_abi.PROTOTYPES) == 74
+    assert lib.fdn_spectral_abi_version() == fdn_hip.SPECTRAL_ABI_VERSION == 1 and len(_abi_spectral.PROTOTYPES) == 5
+    spec = importlib.util.spec_from_file_location("gen_abi_table", os.path.join(ROOT, "tools", "gen_abi_table.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    header = os.path.join(ROOT, "include", "fdn_lowlight.h")
+    assert list(_abi_lowlight.PROTOTYPES.items()) == list(gen.parse_header(header).items())
+    assert list(_abi_lowlight.ARG_NAMES.items()) == list(gen.parse_names(header).items())
+    assert list(_abi_lowlight.PROTOTYPES) == NAMES
+    assert _abi_lowlight.PROTOTYPES["fdn_loe_sample_dims"] == ("I", ["I", "I", "I", "P", "P"])
+    assert _abi_lowlight.PROTOTYPES["fdn_loe_ws"] == ("L", ["I"] * 4) and _abi_lowlight.PROTOTYPES["fdn_deltae00_ws"] == ("L", ["I"] * 3)
+    assert _abi_lowlight.PROTOTYPES["fdn_loe_u8"] == _abi_lowlight.PROTOTYPES["fdn_loe_map_u8"] == ("I", ["P", "P", "I", "I", "I", "I", "P", "P", "P"])
+    assert _abi_lowlight.PROTOTYPES["fdn_deltae00_u8"] == ("I", ["P", "P", "I", "I", "I", "I", "P", "P", "P", "P"])
+    for other in (_abi, _abi_video, _abi_temporal, _abi_vmetrics, _abi_ensemble, _abi_spectral):
+        assert not set(_abi_lowlight.PROTOTYPES) & set(other.PROTOTYPES)
+    assert lib.fdn_loe_ws.restype == ctypes.c_long and lib.fdn_deltae00_ws.restype == ctypes.c_long
+    assert lib.fdn_loe_u8.argtypes == [ctypes.c_void_p] * 2 + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3
+    src = open(os.path.join(ROOT, "fdn-tip2025_amd", "fdn_hip", "lowlight.py")).read()
+    assert "oracle" not in src and "tests" not in src.replace("tests/", "")           # the product path stands without the yardsticks
+
+
+BAD = [dict(B=0), dict(B=-1), dict(h=0), dict(h=-4), dict(w=0), dict(w=-1), dict(h=46341, w=46341), dict(h=2 ** 31 - 1, w=2)]
+
+
+def test_entry_points_validate_arguments_without_gpu(lib):
+    """every refusal of include/fdn_lowlight.h is FDN_ERR_ARG = 1 before any launch (this machine may have no GPU to launch on); the
+    workspace queries answer 0 to the same sizes, and otherwise what the header states"""
+    p = ctypes.c_void_p(64)                          # never dereferenced: every call below fails its argument check
+    md, nd = ctypes.c_int(0), ctypes.c_int(0)
+
+    def loe(a=p, b=p, B=1, h=37, w=53, size=50, ws=p, out=p):
+        return lib.fdn_loe_u8(a, b, B, h, w, size, ws, out, None)
+
+    def loe_map(a=p, b=p, B=1, h=37, w=53, size=50, ws=p, rd=p):
+        return lib.fdn_loe_map_u8(a, b, B, h, w, size, ws, rd, None)
+
+    def de(a=p, b=p, B=1, h=37, w=53, bgr=0, dmap=None, ws=p, out=p):
+        return lib.fdn_deltae00_u8(a, b, B, h, w, bgr, dmap, ws, out, None)
+
+    for key in ("a", "b", "ws", "out"):
+        assert loe(**{key: None}) == 1 and de(**{key: None}) == 1, key
+    for key in ("a", "b", "ws", "rd"):
+        assert loe_map(**{key: None}) == 1, key
+    assert loe(ws=ctypes.c_void_p(72)) == 1 and loe_map(ws=ctypes.c_void_p(72)) == 1            # the tables are read 16 bytes at a time
+    for kw in BAD + [dict(size=-1), dict(size=-50)]:
+        assert loe(**kw) == 1 and loe_map(**kw) == 1, kw
+        args = dict(B=1, h=37, w=53, size=50)
+        args.update(kw)
+        assert lib.fdn_loe_ws(args["B"], args["h"], args["w"], args["size"]) == 0, kw
+        if "B" not in kw:
+            assert lib.fdn_loe_sample_dims(args["h"], args["w"], args["size"], ctypes.byref(md), ctypes.byref(nd)) == 1, kw
+        if "size" not in kw:
+            assert de(**kw) == 1, kw
+            assert lib.fdn_deltae00_ws(args["B"], args["h"], args["w"]) == 0, kw
+    assert lib.fdn_loe_sample_dims(37, 53, 50, None, ctypes.byref(nd)) == 1 and lib.fdn_loe_sample_dims(37, 53, 50, ctypes.byref(md), None) == 1
+    assert lib.fdn_loe_sample_dims(46340, 46340, 50, ctypes.byref(md), ctypes.byref(nd)) == 0 and (md.value, nd.value) == (50, 50)
+    # per image J and C (65536 uint32 each) and R and K (256 each), in 8-byte words, whatever the size of the images
+    per = (2 * 65536 + 512) * 4 // 8
+    assert lowlight.LOE_WS_WORDS == per
+    assert lib.fdn_loe_ws(1, 37, 53, 50) == lib.fdn_loe_ws(1, 720, 1280, 0) == per and lib.fdn_loe_ws(5, 1, 1, 0) == 5 * per
+    assert lib.fdn_loe_ws(2 ** 31 - 1, 1, 1, 0) == (2 ** 31 - 1) * per
+    # {sum, max} per tile of 1024 pixels
+    for B, h, w in ((1, 1, 1), (1, 32, 32), (1, 37, 53), (3, 720, 1280), (2, 46340, 46340)):
+        assert lib.fdn_deltae00_ws(B, h, w) == 2 * B * -(-h * w // 1024), (B, h, w)
+
+
+def test_wrappers_refuse():
+    """no host fallback: CPU tensors without a device, wrong dtypes, mismatched shapes, bad sizes - FdnHipError naming the problem"""
+    from fdn_hip import FdnHipError
+    u = np.zeros((6, 8, 3), np.uint8)
+    for f in (lowlight.loe_u8, lowlight.loe_counts_u8, lowlight.loe_map_u8, lowlight.deltae00_u8, lowlight.lowlight_metrics):
+        with pytest.raises(FdnHipError, match="shapes are different"):
+            f(u, np.zeros((6, 10, 3), np.uint8))
+        with pytest.raises(FdnHipError, match="uint8"):
+            f(u.astype(np.float32), u.astype(np.float32))
+        with pytest.raises(FdnHipError, match="uint8"):
+            f(torch.zeros(1, 3, 6, 8), torch.zeros(1, 3, 6, 8))
+        if not torch.cuda.is_available():
+            with pytest.raises(FdnHipError, match="ROCm"):
+                f(u, u)
+    for size in (-1, 2.5, None, True, 2 ** 31):
+        for f in (lowlight.loe_u8, lowlight.loe_counts_u8, lowlight.loe_map_u8, lowlight.lowlight_metrics):
+            with pytest.raises(FdnHipError, match="size"):
+                f(u, u, size=size)
+        with pytest.raises(FdnHipError, match="size"):
+            lowlight.sample_dims(6, 8, size)
+    with pytest.raises(FdnHipError, match="code 1"):
+        lowlight.sample_dims(0, 8, 50)
+
+
+def _images(tmp_path, names, shape=(40, 72, 3), count=2):
+    from PIL import Image
+    for d in names:
+        (tmp_path / d).mkdir(exist_ok=True)
+        for i in range(count):
+            Image.fromarray(np.zeros(shape, np.uint8)).save(tmp_path / d / f"f{i}.png")
+    return [str(tmp_path / d / "*.png") for d in names]
+
+
+def test_command_line_parsing(tmp_path):
+    """calculate_lowlight_metrics.py: defaults, the bounds of --loe-size and --batch, missing and unequal globs, unequal sizes within a
+    pair; the picture of RD / m"""
+    import calculate_lowlight_metrics as tool
+    lq, rs, gt = _images(tmp_path, ("lq", "rs", "gt"))
+    a = tool.parse_args(["--input", lq, "--restored", rs])
+    assert (a.gt, a.loe_size, a.batch, a.device, a.csv, a.save_loe_map) == (None, 50, 8, "cuda:0", None, None)
+    assert a.items == [(str(tmp_path / "lq" / f"f{i}.png"), str(tmp_path / "rs" / f"f{i}.png")) for i in range(2)]
+    a = tool.parse_args(["--input", lq, "--restored", rs, "--gt", gt, "--loe-size", "0", "--batch", "3", "--device", "cuda:1", "--csv", "x.csv",
+                         "--save-loe-map", "maps"])
+    assert (a.loe_size, a.batch, a.device, a.csv, a.save_loe_map) == (0, 3, "cuda:1", "x.csv", "maps")
+    assert a.items == [tuple(str(tmp_path / d / f"f{i}.png") for d in ("lq", "rs", "gt")) for i in range(2)]
+    for extra in (["--loe-size", "-1"], ["--loe-size", "x"], ["--batch", "0"]):
+        with pytest.raises(SystemExit):
+            tool.parse_args(["--input", lq, "--restored", rs] + extra)
+    one = str(tmp_path / "rs" / "f0.png")
+    for argv in (["--input", lq], ["--restored", rs], ["--input", lq, "--restored", one], ["--input", str(tmp_path / "none*"), "--restored", rs],
+                 ["--input", lq, "--restored", rs, "--gt", str(tmp_path / "gt" / "f1.png")], ["--input", lq, "--restored", rs, "--gt", str(tmp_path / "no*")]):
+        with pytest.raises(SystemExit):
+            tool.parse_args(argv)
+    # sizes are read from the headers before anything is decoded or any device is touched
+    (small,) = _images(tmp_path, ("small",), shape=(40, 70, 3))
+    for items, word in ((tool.match_paths(lq, small), "input"), (tool.match_paths(small, rs), "input"), (tool.match_paths(lq, rs, small), "ground truth")):
+        with pytest.raises(ValueError, match=word):
+            next(tool.decoded_groups(items, 8, None))
+    assert tool.lowlight_line({"loe": 12.5}) == "LOE: 12.500000"
+    assert tool.lowlight_line({"loe": 12.5, "deltae": 3.25, "deltae_max": 9.0}) == "LOE: 12.500000, dE00: 3.250000"
+    px = tool.map_bytes(np.array([[0, 40], [100, 25]], np.uint32), 100)
+    assert px.dtype == np.uint8 and px.tolist() == [[0, 102], [255, 64]]
+
+
+def test_validate_fdn_parser_keeps_its_old_command_lines(tmp_path):
+    """without --lowlight the namespace is what it was: no new attribute; with it the two new ones are set"""
+    import validate_fdn
+    lq, gt = _images(tmp_path, ("lq", "gt"))
+    base = ["--fdn", "x.pth", "--lq", lq, "--gt", gt]
+    old = {"fdn", "lpnet", "lq", "gt", "variant", "ratio", "crop_border", "output", "csv", "batch", "device", "tile", "tile_overlap", "tile_ratio",
+           "tile_blend", "ensemble", "dest", "pairs", "fourier", "fourier_bands"}
+    for argv in (base, base + ["--fourier", "--fourier-bands", "4"], base + ["--csv", "s.csv", "--crop_border", "4", "--batch", "2"],
+                 base + ["--variant", "lolv1", "--ratio", "lpnet", "--lpnet", "l.pth", "--output", str(tmp_path / "out")],
+                 base + ["--tile", "32x32", "--tile-overlap", "8", "--ensemble", "4"]):
+        assert set(vars(validate_fdn.parse_args(argv))) == old, argv
+    a = validate_fdn.parse_args(base + ["--lowlight"])
+    assert a.lowlight is True and not hasattr(a, "loe_size") and set(vars(a)) == old | {"lowlight"}
+    a = validate_fdn.parse_args(base + ["--lowlight", "--loe-size", "0", "--fourier"])
+    assert a.lowlight is True and a.loe_size == 0 and a.fourier is True
+    for bad in (["--loe-size", "50"], ["--lowlight", "--loe-size", "-1"], ["--lowlight", "--loe-size", "x"]):
+        with pytest.raises(SystemExit):
+            validate_fdn.parse_args(base + bad)
+
+
+def test_kernel_table_of_the_dependency():
+    """libfdn_hip.so reaches the new code through its dependency libfdn_lowlight.so, whose code objects tests/kernel_table.txt does not
+    see; tests/kernel_table_lowlight.txt is its table on the same terms: one row per compiled kernel, each with a host stub and a GPU test
+    file that launches it (a kernel trace of that file alone showed all six dispatched).  No kernel sits in both."""
+    import fdn_hip
+    spec = importlib.util.spec_from_file_location("kernel_coverage", os.path.join(ROOT, "tools", "kernel_coverage.py"))
+    cov = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(cov)
+    if not os.path.isfile(fdn_hip.lib_path()):
+        entry.build()
+    dep = os.path.join(os.path.dirname(fdn_hip.lib_path()), "libfdn_lowlight.so")
+    compiled = cov.compiled(dep)
+    rows = cov.read_table(os.path.join(ROOT, "tests", "kernel_table_lowlight.txt"))
+    assert set(rows) == set(compiled), (sorted(set(compiled) - set(rows)), sorted(set(rows) - set(compiled)))
+    for k, (dem, stub) in compiled.items():
+        assert stub, f"{dem}: no host code launches it"
+        assert rows[k][0] == dem, k
+        files = rows[k][1].split()
+        assert files and all(f.startswith("test_gpu_") and os.path.isfile(os.path.join(ROOT, "tests", f)) for f in files), (dem, files)
+    assert not set(cov.compiled(fdn_hip.lib_path())) & set(compiled)
