@@ -262,7 +262,7 @@ int d4_mean(const float* res_a, const float* res_b, void* out, int B, int h, int
 
 }  // namespace
 
-extern "C" int fdn_ensemble_abi_version(void) { return 1; }
+extern "C" int fdn_ensemble_abi_version(void) { return FDN_ENSEMBLE_ABI_VERSION; }
 
 extern "C" int fdn_d4_pre_u8(const unsigned char* img, float* out, int B, int h, int w, int H, int W, int mask, int swap_rb,
                              fdn_stream_t stream) {

@@ -1,6 +1,5 @@
 // Low-light evaluation (include/fdn_lowlight.h): the lightness order error of an input against its enhanced version, and the CIEDE2000
-// colour difference of a restored image against its ground truth, both from 8-bit images [B][h][w][3].  build.sh links this file's
-// object into libfdn_lowlight.so, a dependency of libfdn_hip.so.
+// colour difference of a restored image against its ground truth, both from 8-bit images [B][h][w][3].
 //   fdn_loe_u8      : LOE from the 256 x 256 joint histogram J of (La, Lb), L = max(R, G, B) - no pair of pixels is compared:
 //                     loe_zero_kernel    J = 0 (a launch zeroes what it accumulates into)
 //                     loe_hist_kernel    a workgroup counts up to CHUNK samples in a private histogram in LDS, then adds the bins it
@@ -320,7 +319,7 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 
 }  // namespace
 
-extern "C" int fdn_lowlight_abi_version(void) { return 1; }
+extern "C" int fdn_lowlight_abi_version(void) { return FDN_LOWLIGHT_ABI_VERSION; }
 
 extern "C" int fdn_loe_sample_dims(int h, int w, int size, int* md, int* nd) {
     FDN_CHECK_ARG(md && nd && sample_dims(h, w, size, md, nd));

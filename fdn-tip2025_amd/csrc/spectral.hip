@@ -103,7 +103,7 @@ __global__ __launch_bounds__(THREADS) void pair_bands_fold_kernel(const double* 
 
 }  // namespace
 
-extern "C" int fdn_spectral_abi_version(void) { return 1; }
+extern "C" int fdn_spectral_abi_version(void) { return FDN_SPECTRAL_ABI_VERSION; }
 
 extern "C" int fdn_spectrum_band_counts(int H, int W, int nb, long* counts) {
     FDN_CHECK_ARG(counts && shape_ok(H, W, nb));

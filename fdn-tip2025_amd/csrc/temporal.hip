@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256) void ratio_smooth_kernel(const unsigned* __res
 
 }  // namespace
 
-extern "C" int fdn_temporal_abi_version(void) { return 1; }
+extern "C" int fdn_temporal_abi_version(void) { return FDN_TEMPORAL_ABI_VERSION; }
 
 extern "C" int fdn_luma_hist(const void* frames, unsigned* hist, int B, int h, int w, int bits, fdn_stream_t stream) {
     FDN_CHECK_ARG(frames && hist && B > 0 && B < 65536 && h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0 && (bits == 8 || bits == 10));

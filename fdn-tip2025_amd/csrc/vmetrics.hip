@@ -187,7 +187,7 @@ void launch_stats(const void* a, const void* b, unsigned long long* stats, int B
 
 }  // namespace
 
-extern "C" int fdn_vmetrics_abi_version(void) { return 1; }
+extern "C" int fdn_vmetrics_abi_version(void) { return FDN_VMETRICS_ABI_VERSION; }
 
 extern "C" int fdn_yuv420_pair_stats(const void* a, const void* b, long* stats, int B, int h, int w, int layout, int bits,
                                      fdn_stream_t stream) {

@@ -146,7 +146,7 @@ void yuv_matrix(int matrix, double& kr, double& kg, double& kb) {
 
 }  // namespace
 
-extern "C" int fdn_video_abi_version(void) { return 1; }
+extern "C" int fdn_video_abi_version(void) { return FDN_VIDEO_ABI_VERSION; }
 
 extern "C" int fdn_pre_yuv420(const void* frames, float* out, int B, int h, int w, int H, int W, int layout, int bits, int matrix,
                               int full_range, int chroma_loc, fdn_stream_t stream) {

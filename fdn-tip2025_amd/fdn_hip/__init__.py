@@ -1,5 +1,4 @@
-"""ctypes binding of libfdn_hip.so (the C ABI declared in include/fdn_hip.h, include/fdn_video.h, include/fdn_temporal.h,
-include/fdn_vmetrics.h, include/fdn_ensemble.h, include/fdn_spectral.h and include/fdn_lowlight.h).
+"""ctypes binding of libfdn_hip.so (the C ABI declared in the headers of include/; fdn_hip/_abi.py is their one prototype table).
 
 PyTorch is plumbing here: it owns device memory and the current HIP stream; every compute step
 of the FDN path is a call into the library.  There is NO CPU or eager fallback: if the shared
@@ -9,6 +8,8 @@ import ctypes
 import os
 
 import torch
+
+from ._abi import PROTOTYPES, VERSIONS      # generated from the headers of include/ by tools/gen_abi_table.py
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libfdn_hip.so")      # (measurement tools that A/B another build of the same ABI set this before lib())
@@ -38,13 +39,9 @@ class FdnHipError(RuntimeError):
     pass
 
 
-ABI_VERSION = 22        # include/fdn_hip.h: bumped on any signature change
-VIDEO_ABI_VERSION = 1   # include/fdn_video.h (the video frame entry points), likewise
-TEMPORAL_ABI_VERSION = 1  # include/fdn_temporal.h (the ratio filter across frames), likewise
-VMETRICS_ABI_VERSION = 1  # include/fdn_vmetrics.h (video evaluation from codec samples), likewise
-ENSEMBLE_ABI_VERSION = 1  # include/fdn_ensemble.h (the flipped and transposed copies of the self-ensemble), likewise
-SPECTRAL_ABI_VERSION = 1  # include/fdn_spectral.h (Fourier evaluation: the complex spectrum, the error per band in amplitude and phase), likewise
-LOWLIGHT_ABI_VERSION = 1  # include/fdn_lowlight.h (low-light evaluation: lightness order error, CIEDE2000), likewise
+ABI_VERSION = VERSIONS["fdn_hip.h"][1]      # 22: each header's #define is where its version is typed; bumped on any signature change
+# the other headers by part: {"video": 1, "temporal": 1, ...} ("fdn_video.h" -> "video")
+PART_ABI_VERSIONS = {h[len("fdn_"):-len(".h")]: v for h, (_, v) in VERSIONS.items() if h != "fdn_hip.h"}
 
 
 def lib_path():
@@ -61,51 +58,20 @@ def lib():
                 "The FDN path has no CPU fallback.")
         _lib = ctypes.CDLL(_LIB_PATH)
         _declare(_lib)
-        if _lib.fdn_abi_version() != ABI_VERSION:
-            v = _lib.fdn_abi_version()
-            _lib = None
-            raise ImportError(f"{_LIB_PATH} has ABI version {v}, this binding needs {ABI_VERSION}: rebuild with build.sh")
-        if _lib.fdn_video_abi_version() != VIDEO_ABI_VERSION:
-            v = _lib.fdn_video_abi_version()
-            _lib = None
-            raise ImportError(f"{_LIB_PATH} has video ABI version {v}, this binding needs {VIDEO_ABI_VERSION}: rebuild with build.sh")
-        if _lib.fdn_temporal_abi_version() != TEMPORAL_ABI_VERSION:
-            v = _lib.fdn_temporal_abi_version()
-            _lib = None
-            raise ImportError(f"{_LIB_PATH} has temporal ABI version {v}, this binding needs {TEMPORAL_ABI_VERSION}: rebuild with build.sh")
-        if _lib.fdn_vmetrics_abi_version() != VMETRICS_ABI_VERSION:
-            v = _lib.fdn_vmetrics_abi_version()
-            _lib = None
-            raise ImportError(f"{_LIB_PATH} has vmetrics ABI version {v}, this binding needs {VMETRICS_ABI_VERSION}: rebuild with build.sh")
-        if _lib.fdn_ensemble_abi_version() != ENSEMBLE_ABI_VERSION:
-            v = _lib.fdn_ensemble_abi_version()
-            _lib = None
-            raise ImportError(f"{_LIB_PATH} has ensemble ABI version {v}, this binding needs {ENSEMBLE_ABI_VERSION}: rebuild with build.sh")
-        if _lib.fdn_spectral_abi_version() != SPECTRAL_ABI_VERSION:
-            v = _lib.fdn_spectral_abi_version()
-            _lib = None
-            raise ImportError(f"{_LIB_PATH} has spectral ABI version {v}, this binding needs {SPECTRAL_ABI_VERSION}: rebuild with build.sh")
-        if _lib.fdn_lowlight_abi_version() != LOWLIGHT_ABI_VERSION:
-            v = _lib.fdn_lowlight_abi_version()
-            _lib = None
-            raise ImportError(f"{_LIB_PATH} has lowlight ABI version {v}, this binding needs {LOWLIGHT_ABI_VERSION}: rebuild with build.sh")
+        for h, (fn, need) in VERSIONS.items():
+            v = getattr(_lib, fn)()
+            if v != need:
+                part = "" if h == "fdn_hip.h" else h[len("fdn_"):-len(".h")] + " "
+                _lib = None
+                raise ImportError(f"{_LIB_PATH} has {part}ABI version {v}, this binding needs {need}: rebuild with build.sh")
     return _lib
 
 
 def _declare(l, missing_ok=False):
     """argtypes / restype of every entry point (a wrong argument count or kind raises here instead of corrupting the call).
     missing_ok: skip the entry points `l` lacks (tools/ab_libs.py loads builds of an older ABI beside this one)."""
-    from ._abi import PROTOTYPES
-    from ._abi_video import PROTOTYPES as VIDEO_PROTOTYPES
-    from ._abi_temporal import PROTOTYPES as TEMPORAL_PROTOTYPES
-    from ._abi_vmetrics import PROTOTYPES as VMETRICS_PROTOTYPES
-    from ._abi_ensemble import PROTOTYPES as ENSEMBLE_PROTOTYPES
-    from ._abi_spectral import PROTOTYPES as SPECTRAL_PROTOTYPES
-    from ._abi_lowlight import PROTOTYPES as LOWLIGHT_PROTOTYPES
     kinds = {"P": ctypes.c_void_p, "I": ctypes.c_int, "L": ctypes.c_long, "F": ctypes.c_float, "DESC": ctypes.POINTER(Conv1x1Desc)}
-    tables = (PROTOTYPES, VIDEO_PROTOTYPES, TEMPORAL_PROTOTYPES, VMETRICS_PROTOTYPES, ENSEMBLE_PROTOTYPES, SPECTRAL_PROTOTYPES,
-              LOWLIGHT_PROTOTYPES)
-    for name, (ret, sig) in [item for t in tables for item in t.items()]:
+    for name, (ret, sig) in PROTOTYPES.items():
         f = getattr(l, name, None) if missing_ok else getattr(l, name)      # AttributeError: the library lacks a symbol the header declares
         if f is None:
             continue
@@ -201,6 +167,18 @@ def dev(t, what="tensor"):
         raise FdnHipError(f"{what} must be float32 (got {t.dtype})")
     if not t.is_contiguous():
         raise FdnHipError(f"{what} must be contiguous")
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def ptr(t):
+    """device pointer of a tensor the caller has validated (None stays None: an optional argument of the C ABI)"""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def dev_as(t, dtype, what):
+    """dev() for any dtype, with one message: the pointer of a contiguous `dtype` ROCm tensor, anything else raises"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+        raise FdnHipError(f"{what} must be a contiguous {str(dtype).replace('torch.', '')} ROCm tensor")
     return ctypes.c_void_p(t.data_ptr())
 
 

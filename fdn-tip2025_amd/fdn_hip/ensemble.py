@@ -16,7 +16,7 @@ import ctypes
 
 import torch
 
-from . import FdnHipError, check, lib, stream
+from . import FdnHipError, check, dev_as, lib, stream
 
 MASKS = {1: 0x01, 2: 0x03, 4: 0x0F, 8: 0xFF}
 
@@ -49,12 +49,6 @@ def _half(mask):
     return bool(mask & 0xF0)
 
 
-def _ptr(t, dtype, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
-        raise FdnHipError(f"{what} must be a contiguous {str(dtype).replace('torch.', '')} ROCm tensor")
-    return ctypes.c_void_p(t.data_ptr())
-
-
 def _copies(src, dtype, what, mask, pad, call):
     """the body of pre_u8 / apply: src [B,h,w,3] uint8 or [N,3,h,w] float32 -> (out [K,B,3,H,W], h', w')"""
     from .harness import padded_size
@@ -66,7 +60,7 @@ def _copies(src, dtype, what, mask, pad, call):
     H, W = padded_size(hp, wp) if pad else (hp, wp)
     if H - hp >= hp or W - wp >= wp:
         raise FdnHipError(f"reflect padding {hp}x{wp} -> {H}x{W} needs pad < size (F.pad raises the same way)")
-    p = _ptr(src, dtype, what)
+    p = dev_as(src, dtype, what)
     out = torch.empty((len(ks), B, 3, H, W), device=src.device, dtype=torch.float32)
     call(p, ctypes.c_void_p(out.data_ptr()), B, h, w, H, W)
     return out, hp, wp
@@ -104,7 +98,7 @@ def _results(res_a, res_b, mask, h, w):
             dims += [0, 0]
             ptrs.append(None)
             continue
-        ptrs.append(_ptr(res, torch.float32, name))
+        ptrs.append(dev_as(res, torch.float32, name))
         if res.dim() != 5 or res.shape[0] != K or res.shape[2] != 3 or res.shape[3] < hp or res.shape[4] < wp or \
                 (B is not None and res.shape[1] != B):
             raise FdnHipError(f"{name} must be [{K},B,3,>={hp},>={wp}], got {tuple(res.shape)}")

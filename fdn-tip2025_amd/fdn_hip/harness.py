@@ -33,13 +33,7 @@ from dataclasses import dataclass
 
 import torch
 
-from . import lib, check, stream, FdnHipError
-
-
-def _u8(t, what):
-    if not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous():
-        raise FdnHipError(f"{what} must be a contiguous uint8 ROCm tensor")
-    return ctypes.c_void_p(t.data_ptr())
+from . import lib, check, dev_as, stream, FdnHipError
 
 
 def padded_size(h, w, multiple=32):
@@ -58,7 +52,7 @@ def preprocess(img_u8, bgr=True):
     if H - h >= h or W - w >= w:
         raise FdnHipError(f"reflect padding {h}x{w} -> {H}x{W} needs pad < size (F.pad raises the same way)")
     out = torch.empty((B, 3, H, W), device=img_u8.device, dtype=torch.float32)
-    check(lib().fdn_pre_u8(_u8(img_u8, "img"), ctypes.c_void_p(out.data_ptr()), B, h, w, H, W, int(bool(bgr)), stream()),
+    check(lib().fdn_pre_u8(dev_as(img_u8, torch.uint8, "img"), ctypes.c_void_p(out.data_ptr()), B, h, w, H, W, int(bool(bgr)), stream()),
           "fdn_pre_u8")
     return out, h, w
 
@@ -71,7 +65,7 @@ def postprocess(result, h, w, bgr=True):
     if C != 3 or h > H or w > W:
         raise FdnHipError(f"cannot crop {h}x{w} out of {tuple(result.shape)}")
     out = torch.empty((B, h, w, 3), device=result.device, dtype=torch.uint8)
-    check(lib().fdn_post_u8(ctypes.c_void_p(result.data_ptr()), _u8(out, "out"), B, h, w, H, W, int(bool(bgr)), stream()),
+    check(lib().fdn_post_u8(ctypes.c_void_p(result.data_ptr()), dev_as(out, torch.uint8, "out"), B, h, w, H, W, int(bool(bgr)), stream()),
           "fdn_post_u8")
     return out
 
@@ -107,8 +101,8 @@ def _frame_f32(img_u8, bgr):
     h, w, _ = img_u8.shape
     ij = torch.zeros((1, 2), dtype=torch.int32, device=img_u8.device)
     out = torch.empty((1, 3, h, w), device=img_u8.device, dtype=torch.float32)
-    check(lib().fdn_tiles_gather_u8(_u8(img_u8, "img"), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ij.data_ptr()), 1, h, w, h, w,
-                                    int(bool(bgr)), stream()), "fdn_tiles_gather_u8")
+    check(lib().fdn_tiles_gather_u8(dev_as(img_u8, torch.uint8, "img"), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ij.data_ptr()), 1,
+                                    h, w, h, w, int(bool(bgr)), stream()), "fdn_tiles_gather_u8")
     return out
 
 

@@ -20,13 +20,9 @@ import ctypes
 
 import torch
 
-from . import FdnHipError, check, lib, stream
+from . import FdnHipError, check, lib, ptr, stream
 
 LOE_WS_WORDS = 65792            # 8-byte words of workspace per image: uint32 J[256][256], C[256][256], R[256], K[256]
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _size(size):
@@ -58,7 +54,7 @@ def _loe_launch(a, b, size, out):
         raise FdnHipError(f"fdn_loe_ws refuses {B} images of {h}x{w} at size {size}")
     ws = torch.empty(nws, dtype=torch.int64, device=a.device)
     with torch.cuda.device(a.device):
-        check(lib().fdn_loe_u8(_ptr(a), _ptr(b), B, h, w, size, _ptr(ws), _ptr(out), stream()), "fdn_loe_u8")
+        check(lib().fdn_loe_u8(ptr(a), ptr(b), B, h, w, size, ptr(ws), ptr(out), stream()), "fdn_loe_u8")
     return ws
 
 
@@ -89,7 +85,7 @@ def loe_map_u8(inp, enh, size=50):
     ws = _loe_launch(a, b, size, out)
     rd = torch.empty((B, md, nd), dtype=torch.uint32, device=a.device)
     with torch.cuda.device(a.device):
-        check(lib().fdn_loe_map_u8(_ptr(a), _ptr(b), B, h, w, size, _ptr(ws), _ptr(rd), stream()), "fdn_loe_map_u8")
+        check(lib().fdn_loe_map_u8(ptr(a), ptr(b), B, h, w, size, ptr(ws), ptr(rd), stream()), "fdn_loe_map_u8")
     return rd
 
 
@@ -101,7 +97,7 @@ def _deltae_launch(a, b, bgr, out, want_map):
     ws = torch.empty(nws, dtype=torch.float64, device=a.device)
     dmap = torch.empty((B, h, w), dtype=torch.float32, device=a.device) if want_map else None
     with torch.cuda.device(a.device):
-        check(lib().fdn_deltae00_u8(_ptr(a), _ptr(b), B, h, w, int(bool(bgr)), _ptr(dmap), _ptr(ws), _ptr(out), stream()), "fdn_deltae00_u8")
+        check(lib().fdn_deltae00_u8(ptr(a), ptr(b), B, h, w, int(bool(bgr)), ptr(dmap), ptr(ws), ptr(out), stream()), "fdn_deltae00_u8")
     return dmap
 
 
@@ -131,7 +127,7 @@ def lowlight_metrics(inp, enh, gt=None, size=50, bgr=True, want_loe_map=False):
     if want_loe_map:
         rd = torch.empty((B,) + sample_dims(h, w, size), dtype=torch.uint32, device=a.device)
         with torch.cuda.device(a.device):
-            check(lib().fdn_loe_map_u8(_ptr(a), _ptr(b), B, h, w, size, _ptr(ws), _ptr(rd), stream()), "fdn_loe_map_u8")
+            check(lib().fdn_loe_map_u8(ptr(a), ptr(b), B, h, w, size, ptr(ws), ptr(rd), stream()), "fdn_loe_map_u8")
     if gt is not None:
         g, e = _pair(gt, enh, "lowlight_metrics")
         if g.device != b.device:

@@ -14,13 +14,12 @@ The weights are the user's (none ship with this package).  Accepted, as files (t
       lpips linear heads weights/v0.1/{vgg,alex}.pth (linK.model.1.weight, shape [1,C,1,1]) as `lin_weights`.
 A missing key, an unexpected key or a wrong shape raises FdnHipError naming the key.  pyiqa's combined LPIPS files are expected to have
 layout (a); that is untested."""
-import ctypes
 import os
 from collections.abc import Mapping
 
 import torch
 
-from . import ACT_RELU, FdnHipError, check, lib, ops, stream
+from . import ACT_RELU, FdnHipError, check, lib, ops, ptr, stream
 
 SHIFT = (-.030, -.088, -.188)            # ScalingLayer of lpips (float32 on the device, as torch.Tensor of these)
 SCALE = (.458, .448, .450)
@@ -165,10 +164,6 @@ def load_weights(net, weights, lin_weights=None):
     return {"convs": packed, "lins": lins}
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
 def prep_u8(img, bgr=True):
     """uint8 [B][H][W][3] ROCm tensor -> the scaling layer's output float32 [B][3][H][W] (R, G, B), calculate_lpips.py's op order"""
     if not img.is_cuda or img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3:
@@ -176,7 +171,7 @@ def prep_u8(img, bgr=True):
     img = img.contiguous()
     B, H, W, _ = img.shape
     out = torch.empty((B, 3, H, W), dtype=torch.float32, device=img.device)
-    check(lib().fdn_lpips_prep_u8(_ptr(img), _ptr(out), B, H, W, int(bool(bgr)), stream()), "fdn_lpips_prep_u8")
+    check(lib().fdn_lpips_prep_u8(ptr(img), ptr(out), B, H, W, int(bool(bgr)), stream()), "fdn_lpips_prep_u8")
     return out
 
 
@@ -188,7 +183,7 @@ def prep_f32(x, normalize=False, out=None):
     B, _, H, W = x.shape
     if out is None:
         out = torch.empty_like(x)
-    check(lib().fdn_lpips_prep_f32(_ptr(x), _ptr(out), B, H, W, int(bool(normalize)), stream()), "fdn_lpips_prep_f32")
+    check(lib().fdn_lpips_prep_f32(ptr(x), ptr(out), B, H, W, int(bool(normalize)), stream()), "fdn_lpips_prep_f32")
     return out
 
 
@@ -201,7 +196,7 @@ def layer(f, w, out=None, accumulate=False):
     if out is None:
         out = torch.zeros(B, dtype=torch.float64, device=f.device)
     ws = torch.empty(B * LPIPS_PARTS, dtype=torch.float64, device=f.device)
-    check(lib().fdn_lpips_layer(ops._flat(f, "f"), ops._flat(w, "w"), _ptr(out), B, C, H, W, int(bool(accumulate)), _ptr(ws), stream()),
+    check(lib().fdn_lpips_layer(ops._flat(f, "f"), ops._flat(w, "w"), ptr(out), B, C, H, W, int(bool(accumulate)), ptr(ws), stream()),
           "fdn_lpips_layer")
     return out
 

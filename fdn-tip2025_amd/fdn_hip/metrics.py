@@ -18,7 +18,7 @@ import os
 import numpy as np
 import torch
 
-from . import FdnHipError, check, lib, stream
+from . import FdnHipError, check, lib, ptr, stream
 
 
 def _prep(img1, img2, crop_border):
@@ -36,13 +36,9 @@ def _prep(img1, img2, crop_border):
     return out
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
 def _sse_max(a, b):
     acc = torch.zeros(2, dtype=torch.float64, device=a.device)
-    check(lib().fdn_sse_max(_ptr(a), _ptr(b), ctypes.c_long(a.numel()), _ptr(acc), stream()), "fdn_sse_max")
+    check(lib().fdn_sse_max(ptr(a), ptr(b), ctypes.c_long(a.numel()), ptr(acc), stream()), "fdn_sse_max")
     sse, mx = acc.tolist()
     return sse, mx
 
@@ -53,7 +49,7 @@ def to_y_channel(img_bgr):
         raise FdnHipError("to_y_channel needs a 3-channel (B, G, R) image")
     _, H, W = img_bgr.shape
     out = torch.empty((1, H, W), dtype=torch.float32, device=img_bgr.device)
-    check(lib().fdn_y_channel(_ptr(img_bgr), _ptr(out), H, W, stream()), "fdn_y_channel")
+    check(lib().fdn_y_channel(ptr(img_bgr), ptr(out), H, W, stream()), "fdn_y_channel")
     return out
 
 
@@ -73,7 +69,7 @@ def _ssim2d(a, b, max_value, replicate_no_crop):
     C, H, W = a.shape
     ws = torch.empty(5 * a.numel(), dtype=torch.float64, device=a.device)
     acc = torch.zeros(1, dtype=torch.float64, device=a.device)
-    check(lib().fdn_ssim2d(_ptr(a), _ptr(b), C, H, W, ctypes.c_float(max_value), int(replicate_no_crop), _ptr(ws), _ptr(acc), stream()),
+    check(lib().fdn_ssim2d(ptr(a), ptr(b), C, H, W, ctypes.c_float(max_value), int(replicate_no_crop), ptr(ws), ptr(acc), stream()),
           "fdn_ssim2d")
     count = C * H * W if replicate_no_crop else C * (H - 10) * (W - 10)
     return float(acc.item()) / count
@@ -90,7 +86,7 @@ def calculate_ssim(img1, img2, crop_border=0, test_y_channel=False, ssim3d=True)
         return _ssim2d(a, b, max_value, False)                                                         # _ssim, :84-116
     ws = torch.empty(10 * a.numel(), dtype=torch.float32, device=a.device)
     acc = torch.zeros(1, dtype=torch.float64, device=a.device)
-    check(lib().fdn_ssim3d(_ptr(a), _ptr(b), C, H, W, ctypes.c_float(max_value), _ptr(ws), _ptr(acc), stream()), "fdn_ssim3d")
+    check(lib().fdn_ssim3d(ptr(a), ptr(b), C, H, W, ctypes.c_float(max_value), ptr(ws), ptr(acc), stream()), "fdn_ssim3d")
     return float(acc.item()) / a.numel()
 
 
@@ -180,9 +176,9 @@ def calculate_psnr_ssim_u8(img1, img2, crop_border=0, test_y_channel=False, ssim
         taps, mix = ssim3d_taps(), np.ascontiguousarray(ssim3d_channel_matrix())
         with torch.cuda.device(a.device):
             s = stream()
-            check(l.fdn_pair_sse_u8(_ptr(a), _ptr(b), B, h, w, cb, _ptr(stats), s), "fdn_pair_sse_u8")
-            check(l.fdn_pair_ssim3d_u8(_ptr(a), _ptr(b), B, h, w, cb, _ptr(stats), taps.ctypes.data_as(ctypes.c_void_p),
-                                       mix.ctypes.data_as(ctypes.c_void_p), _ptr(ws), _ptr(out), s), "fdn_pair_ssim3d_u8")
+            check(l.fdn_pair_sse_u8(ptr(a), ptr(b), B, h, w, cb, ptr(stats), s), "fdn_pair_sse_u8")
+            check(l.fdn_pair_ssim3d_u8(ptr(a), ptr(b), B, h, w, cb, ptr(stats), taps.ctypes.data_as(ctypes.c_void_p),
+                                       mix.ctypes.data_as(ctypes.c_void_p), ptr(ws), ptr(out), s), "fdn_pair_ssim3d_u8")
         res = out.cpu().tolist()                                                                       # the one copy: [B][sse, max, ssim]
         n = 3 * (h - 2 * cb) * (w - 2 * cb)
         psnr = [_psnr_from_sse(int(r[0]), r[1], n) for r in res]
@@ -285,12 +281,12 @@ def niqe_features(img, crop_border=0, input_order="CHW", convert_to="y", window=
     tables = _niqe_tables_on(dev)
     l, s = lib(), stream()
     wp = win.ctypes.data_as(ctypes.c_void_p)
-    check(l.fdn_niqe_luma(_ptr(x), _ptr(plane), B, C, Hs, Ws, cb, cb, H, W, mode, s), "fdn_niqe_luma")
-    check(l.fdn_niqe_mscn(_ptr(plane), _ptr(mscn1), B, H, W, 0, wp, s), "fdn_niqe_mscn")
-    check(l.fdn_niqe_mscn(_ptr(plane), _ptr(mscn2), B, H // 2, W // 2, 1, wp, s), "fdn_niqe_mscn")
+    check(l.fdn_niqe_luma(ptr(x), ptr(plane), B, C, Hs, Ws, cb, cb, H, W, mode, s), "fdn_niqe_luma")
+    check(l.fdn_niqe_mscn(ptr(plane), ptr(mscn1), B, H, W, 0, wp, s), "fdn_niqe_mscn")
+    check(l.fdn_niqe_mscn(ptr(plane), ptr(mscn2), B, H // 2, W // 2, 1, wp, s), "fdn_niqe_mscn")
     ntab = tables.shape[1]
-    check(l.fdn_niqe_features(_ptr(mscn1), _ptr(feats[0]), B, H, W, NIQE_BLOCK, _ptr(tables), ntab, s), "fdn_niqe_features")
-    check(l.fdn_niqe_features(_ptr(mscn2), _ptr(feats[1]), B, H // 2, W // 2, NIQE_BLOCK // 2, _ptr(tables), ntab, s), "fdn_niqe_features")
+    check(l.fdn_niqe_features(ptr(mscn1), ptr(feats[0]), B, H, W, NIQE_BLOCK, ptr(tables), ntab, s), "fdn_niqe_features")
+    check(l.fdn_niqe_features(ptr(mscn2), ptr(feats[1]), B, H // 2, W // 2, NIQE_BLOCK // 2, ptr(tables), ntab, s), "fdn_niqe_features")
     return {"plane": plane, "mscn1": mscn1, "mscn2": mscn2, "feats": feats}
 
 

@@ -20,15 +20,11 @@ import math
 import numpy as np
 import torch
 
-from . import FdnHipError, check, lib, stream
+from . import FdnHipError, check, lib, ptr, stream
 from . import ops
 
 TERMS = 5                       # per band: total, amplitude part, phase part, the ground truth's energy, sum |dRe| + |dIm|
 MAX_H, MAX_W, MAX_BANDS = 4096, 10240, 32
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def _bands(bands):
@@ -65,7 +61,7 @@ def _rfft2(x):
     H, W = x.shape[-2:]
     with torch.cuda.device(x.device):
         z = ops.rfft_rows(x)
-        check(lib().fdn_fft_cols_c2c(_ptr(z), ctypes.c_long(x.numel() // (H * W)), H, W // 2 + 1, stream()), "fdn_fft_cols_c2c")
+        check(lib().fdn_fft_cols_c2c(ptr(z), ctypes.c_long(x.numel() // (H * W)), H, W // 2 + 1, stream()), "fdn_fft_cols_c2c")
     return z
 
 
@@ -109,7 +105,7 @@ def spectrum_pair_bands(za, zb, H, W, bands=8):
     ws = torch.empty(nws, dtype=torch.float64, device=za.device)
     out = torch.empty((n, bands + 1, TERMS), dtype=torch.float64, device=za.device)
     with torch.cuda.device(za.device):
-        check(lib().fdn_spectrum_pair_bands(_ptr(za), _ptr(zb), _ptr(out), _ptr(ws), ctypes.c_long(n), H, W, ctypes.c_long(za.shape[-2]),
+        check(lib().fdn_spectrum_pair_bands(ptr(za), ptr(zb), ptr(out), ptr(ws), ctypes.c_long(n), H, W, ctypes.c_long(za.shape[-2]),
                                             bands, stream()), "fdn_spectrum_pair_bands")
     return out
 
@@ -186,7 +182,7 @@ def _u8_planes(img1, img2, bgr):
     with torch.cuda.device(a.device):
         for t in (a, b):
             p = torch.empty((B, 3, h, w), device=t.device, dtype=torch.float32)
-            check(lib().fdn_pre_u8(_ptr(t), _ptr(p), B, h, w, h, w, int(bool(bgr)), stream()), "fdn_pre_u8")
+            check(lib().fdn_pre_u8(ptr(t), ptr(p), B, h, w, h, w, int(bool(bgr)), stream()), "fdn_pre_u8")
             out.append(p)
     return out[0], out[1], single
 

@@ -6,19 +6,14 @@ flickers.  RatioFilter keeps it steady: a causal exponential moving average per 
 is found by the distance between the luma histograms of neighbouring frames.  Histogram, cut decision and filter run on the GPU
 (fdn_luma_hist, fdn_ratio_smooth), where the codec samples and LPNet's ratio already are: no host round trip between LPNet and FDN.
 """
-import ctypes
 import math
 from fractions import Fraction
 
 import torch
 
-from . import lib, check, stream, FdnHipError
+from . import lib, check, ptr, stream, FdnHipError
 
 STATE_WORDS = 258        # FDN_TEMPORAL_STATE_WORDS: histogram of the last frame, bits of the last filtered ratio, flags
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 class RatioFilter:
@@ -91,9 +86,9 @@ class RatioFilter:
             self._dist = torch.empty(B, dtype=torch.int32, device=self.device)
             self._cut = torch.empty(B, dtype=torch.int32, device=self.device)
         out = torch.empty_like(ratio)
-        check(lib().fdn_luma_hist(_ptr(frames), _ptr(self._hist), B, self.h, self.w, self.bits, stream()), "fdn_luma_hist")
-        check(lib().fdn_ratio_smooth(_ptr(self._hist), _ptr(ratio), _ptr(self.state), self.alpha, self.cut_above, B, _ptr(out),
-                                     _ptr(self._dist), _ptr(self._cut), stream()), "fdn_ratio_smooth")
+        check(lib().fdn_luma_hist(ptr(frames), ptr(self._hist), B, self.h, self.w, self.bits, stream()), "fdn_luma_hist")
+        check(lib().fdn_ratio_smooth(ptr(self._hist), ptr(ratio), ptr(self.state), self.alpha, self.cut_above, B, ptr(out),
+                                     ptr(self._dist), ptr(self._cut), stream()), "fdn_ratio_smooth")
         self.last_cut, self.last_dist = self._cut[:B], self._dist[:B]
         self._cuts += self.last_cut.sum()
         return out

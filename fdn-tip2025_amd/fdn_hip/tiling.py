@@ -7,13 +7,14 @@ feature of the reference being mirrored, not an optimisation.  scale = 1 (restor
 blend="feather" is this project's own option beside that average: the tiles are weighted with linear ramps across their overlaps
 (feather_weights), so the merged frame has no step where one tile's coverage ends.  The default everywhere is the reference's average.
 """
-import ctypes
 import math
 
 import numpy as np
 import torch
 
-from . import FdnHipError, check, lib, stream
+from . import FdnHipError, check, dev_as, lib, ptr, stream
+
+F32, U8 = torch.float32, torch.uint8
 
 
 # The largest reflect-padded frame a whole-frame forward is pinned at by the GPU suite (tests/test_gpu_configs.py, BASELINE.json
@@ -74,12 +75,6 @@ def effective_crop(h, w, crop_h, crop_w):
     return min(crop_h, h // 32 * 32), min(crop_w, w // 32 * 32)
 
 
-def _f32(t, what):
-    if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
-        raise FdnHipError(f"{what} must be a contiguous float32 ROCm tensor")
-    return ctypes.c_void_p(t.data_ptr())
-
-
 def split(x, crop_h, crop_w, overlap=0):
     """grids(): x (1,C,h,w) -> (tiles (T,C,crop_h,crop_w), origins tensor int32 [T,2] on the device)."""
     if x.dim() != 4 or x.shape[0] != 1:
@@ -88,7 +83,7 @@ def split(x, crop_h, crop_w, overlap=0):
     idx = tile_origins(h, w, crop_h, crop_w, overlap)
     ij = torch.tensor(idx, dtype=torch.int32, device=x.device)
     tiles = torch.empty((len(idx), C, crop_h, crop_w), device=x.device, dtype=torch.float32)
-    check(lib().fdn_tiles_gather(_f32(x, "x"), _f32(tiles, "tiles"), ctypes.c_void_p(ij.data_ptr()), len(idx), C, h, w, crop_h,
+    check(lib().fdn_tiles_gather(dev_as(x, F32, "x"), dev_as(tiles, F32, "tiles"), ptr(ij), len(idx), C, h, w, crop_h,
                                  crop_w, stream()), "fdn_tiles_gather")
     return tiles, ij
 
@@ -155,18 +150,12 @@ def merge(outs, ij, h, w, blend="average"):
         if tuple(ij.shape) != (T, 2):
             raise FdnHipError(f"cannot merge tiles {tuple(outs.shape)} with origins {tuple(ij.shape)}")
         wy, wx = _feather_on_device(ij, ch, cw)
-        check(lib().fdn_tiles_merge_w(_f32(outs, "outs"), _f32(out, "out"), ctypes.c_void_p(ij.data_ptr()), _f32(wy, "wy"), _f32(wx, "wx"),
+        check(lib().fdn_tiles_merge_w(dev_as(outs, F32, "outs"), dev_as(out, F32, "out"), ptr(ij), dev_as(wy, F32, "wy"), dev_as(wx, F32, "wx"),
                                       T, C, h, w, ch, cw, stream()), "fdn_tiles_merge_w")
         return out
-    check(lib().fdn_tiles_merge(_f32(outs, "outs"), _f32(out, "out"), ctypes.c_void_p(ij.data_ptr()), T, C, h, w, ch, cw, stream()),
+    check(lib().fdn_tiles_merge(dev_as(outs, F32, "outs"), dev_as(out, F32, "out"), ptr(ij), T, C, h, w, ch, cw, stream()),
           "fdn_tiles_merge")
     return out
-
-
-def _u8(t, what):
-    if not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous():
-        raise FdnHipError(f"{what} must be a contiguous uint8 ROCm tensor")
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def split_u8(img_u8, crop_h, crop_w, bgr=True, overlap=0):
@@ -177,10 +166,10 @@ def split_u8(img_u8, crop_h, crop_w, bgr=True, overlap=0):
     h, w, _ = img_u8.shape
     ch, cw = effective_crop(h, w, crop_h, crop_w)
     idx = tile_origins(h, w, ch, cw, overlap)
-    src = _u8(img_u8, "img")
+    src = dev_as(img_u8, U8, "img")
     ij = torch.tensor(idx, dtype=torch.int32, device=img_u8.device)
     tiles = torch.empty((len(idx), 3, ch, cw), device=img_u8.device, dtype=torch.float32)
-    check(lib().fdn_tiles_gather_u8(src, _f32(tiles, "tiles"), ctypes.c_void_p(ij.data_ptr()), len(idx), h, w, ch, cw, int(bool(bgr)),
+    check(lib().fdn_tiles_gather_u8(src, dev_as(tiles, F32, "tiles"), ptr(ij), len(idx), h, w, ch, cw, int(bool(bgr)),
                                     stream()), "fdn_tiles_gather_u8")
     return tiles, ij
 
@@ -195,10 +184,10 @@ def merge_u8(outs, ij, h, w, bgr=True, blend="average"):
     out = torch.empty((h, w, 3), device=outs.device, dtype=torch.uint8)
     if blend == "feather":
         wy, wx = _feather_on_device(ij, ch, cw)
-        check(lib().fdn_tiles_merge_w_u8(_f32(outs, "outs"), _u8(out, "out"), ctypes.c_void_p(ij.data_ptr()), _f32(wy, "wy"), _f32(wx, "wx"),
+        check(lib().fdn_tiles_merge_w_u8(dev_as(outs, F32, "outs"), dev_as(out, U8, "out"), ptr(ij), dev_as(wy, F32, "wy"), dev_as(wx, F32, "wx"),
                                          T, h, w, ch, cw, int(bool(bgr)), stream()), "fdn_tiles_merge_w_u8")
         return out
-    check(lib().fdn_tiles_merge_u8(_f32(outs, "outs"), _u8(out, "out"), ctypes.c_void_p(ij.data_ptr()), T, h, w, ch, cw, int(bool(bgr)),
+    check(lib().fdn_tiles_merge_u8(dev_as(outs, F32, "outs"), dev_as(out, U8, "out"), ptr(ij), T, h, w, ch, cw, int(bool(bgr)),
                                    stream()), "fdn_tiles_merge_u8")
     return out
 

@@ -26,6 +26,7 @@ extern "C" {
 #endif
 
 /* version of this header: bumped on any signature change below */
+#define FDN_ENSEMBLE_ABI_VERSION 1
 int fdn_ensemble_abi_version(void);
 
 /* img uint8 [B][h][w][3] -> out fp32 [K][B][3][H][W], one copy per code of mask in ascending k.  Output pixel (y, x) of copy k is

@@ -37,6 +37,7 @@ enum { FDN_EPI_NONE = 0, FDN_EPI_RES = 1, FDN_EPI_MULADD = 2 };
 enum { FDN_RS_BILINEAR_HALF = 0, FDN_RS_BILINEAR_X2 = 1, FDN_RS_NEAREST_HALF = 2, FDN_RS_NEAREST_X2 = 3, FDN_RS_PIXEL_UNSHUFFLE = 4 };
 
 /* library version / build info: returns the ABI version (bumped on any signature change; 21 since fdn_tiles_gather_u8 / fdn_tiles_merge_u8) */
+#define FDN_ABI_VERSION 22
 int fdn_abi_version(void);
 const char* fdn_error_string(int code);
 /* Diagnostic switch, process-wide, default 0 = every matrix product that has a split-bf16 form runs on the bf16 matrix pipe

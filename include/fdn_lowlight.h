@@ -3,7 +3,6 @@
  *          reversed the relative order of two pixels' lightness.  Needs no ground truth.
  *   dE00   the CIEDE2000 colour difference (Sharma, Wu, Dalal 2005; kL = kC = kH = 1) of a restored image against its ground truth.
  * A header of its own with a version of its own, as include/fdn_spectral.h: fdn_hip.h, the other headers and their versions stand still.
- * (The code sits in libfdn_lowlight.so, which libfdn_hip.so names as a dependency and finds beside itself: link and load libfdn_hip.so.)
  * Conventions as in fdn_hip.h: raw device pointers, nothing allocated or synchronised, work enqueued on `stream`, FDN_OK or an
  * FDN_ERR_* code returned; FDN_ERR_ARG before any launch.  No memory has to be zeroed by the caller: a launch zeroes what it accumulates
  * into.  An image's result does not depend on the other images of the batch and has the same bits on every call.
@@ -38,6 +37,7 @@ extern "C" {
 #endif
 
 /* version of this header: bumped on any signature change below */
+#define FDN_LOWLIGHT_ABI_VERSION 1
 int fdn_lowlight_abi_version(void);
 
 /* md, nd = the sample grid Md x Nd of an h x w image at `size` (the rule above).  Host arithmetic only (no HIP call: answers without a

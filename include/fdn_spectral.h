@@ -28,6 +28,7 @@ extern "C" {
 #endif
 
 /* version of this header: bumped on any signature change below */
+#define FDN_SPECTRAL_ABI_VERSION 1
 int fdn_spectral_abi_version(void);
 
 /* forward FFT along H, in place, of z [planes][H][Wf] interleaved complex, unscaled: with fdn_rfft_rows before it, rfft2.  Wf may be a

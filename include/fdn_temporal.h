@@ -23,6 +23,7 @@ extern "C" {
 #define FDN_TEMPORAL_STATE_WORDS 258
 
 /* version of this header: bumped on any signature change below */
+#define FDN_TEMPORAL_ABI_VERSION 1
 int fdn_temporal_abi_version(void);
 
 /* frames, as fdn_pre_yuv420 takes them: B contiguous frames of h * w * 3 / 2 samples; bits 8: uint8, 10: little-endian uint16 with the

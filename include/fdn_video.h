@@ -28,6 +28,7 @@ extern "C" {
 #endif
 
 /* version of this header: bumped on any signature change below */
+#define FDN_VIDEO_ABI_VERSION 1
 int fdn_video_abi_version(void);
 
 /* frames -> out [B][3][H][W] fp32 R', G', B' in [0, 1].  Output pixel (y, x) is the conversion at source position (sy, sx), reflected

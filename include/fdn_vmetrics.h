@@ -23,6 +23,7 @@ extern "C" {
 #endif
 
 /* version of this header: bumped on any signature change below */
+#define FDN_VMETRICS_ABI_VERSION 1
 int fdn_vmetrics_abi_version(void);
 
 /* frames a, b -> stats [B][5] int64 = { SSE_Y, SSE_Cb, SSE_Cr, sum of a's luma codes, sum of b's luma codes } per frame pair: the sums

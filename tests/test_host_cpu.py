@@ -30,15 +30,75 @@ def test_library_exports_every_declared_symbol(lib):
     assert lib.fdn_error_string(1).decode().startswith("invalid argument")
 
 
-def test_ctypes_prototypes_match_header(lib):
-    """fdn_hip/_abi.py (argtypes of every entry point) is exactly what include/fdn_hip.h declares, and the loader applied it."""
+@pytest.fixture(scope="module")
+def gen():
     import importlib.util
-    import ctypes as C
-    from fdn_hip._abi import PROTOTYPES
     spec = importlib.util.spec_from_file_location("gen_abi_table", os.path.join(ROOT, "tools", "gen_abi_table.py"))
-    gen = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gen)
-    assert PROTOTYPES == gen.parse_header(os.path.join(ROOT, "include", "fdn_hip.h"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+# header -> (entry points, version function, version): a new header is one row here and one entry of tools/gen_abi_table.py HEADERS
+ABI = {"fdn_hip.h": (74, "fdn_abi_version", 22), "fdn_video.h": (3, "fdn_video_abi_version", 1),
+       "fdn_temporal.h": (3, "fdn_temporal_abi_version", 1), "fdn_vmetrics.h": (4, "fdn_vmetrics_abi_version", 1),
+       "fdn_ensemble.h": (5, "fdn_ensemble_abi_version", 1), "fdn_spectral.h": (5, "fdn_spectral_abi_version", 1),
+       "fdn_lowlight.h": (7, "fdn_lowlight_abi_version", 1)}
+
+
+@pytest.mark.parametrize("header", list(ABI))
+def test_version_and_prototype_table(lib, gen, header):
+    """fdn_hip/_abi.py holds, for every header of include/, exactly what it declares, in the headers' order and then the declarations';
+    the library, the table and this test agree on each header's version"""
+    import fdn_hip
+    from fdn_hip._abi import ARG_NAMES, HEADERS, PROTOTYPES, VERSIONS
+    assert list(HEADERS) == list(VERSIONS) == list(ABI) == gen.HEADERS
+    count, fn, version = ABI[header]
+    path = os.path.join(ROOT, "include", header)
+    at = sum(ABI[h][0] for h in list(ABI)[:list(ABI).index(header)])
+    assert HEADERS[header] == list(gen.parse_header(path)) and len(HEADERS[header]) == count
+    assert list(PROTOTYPES.items())[at:at + count] == list(gen.parse_header(path).items())
+    assert list(ARG_NAMES.items())[at:at + count] == list(gen.parse_names(path).items())
+    assert len(PROTOTYPES) == len(ARG_NAMES) == sum(c for c, _, _ in ABI.values()) == 101
+    assert VERSIONS[header] == (fn, version) == gen.parse_version(path) and fn in HEADERS[header]
+    assert getattr(lib, fn)() == version
+    assert fdn_hip.ABI_VERSION == 22
+    assert fdn_hip.PART_ABI_VERSIONS == {"video": 1, "temporal": 1, "vmetrics": 1, "ensemble": 1, "spectral": 1, "lowlight": 1}
+
+
+def test_generator_refuses_a_name_declared_twice(gen, tmp_path):
+    """the tables of two headers cannot share a name: the generator raises instead of letting the later declaration win"""
+    for h in ("fdn_hip.h", "fdn_video.h"):
+        (tmp_path / h).write_text(open(os.path.join(ROOT, "include", h)).read())
+    assert len(gen.build_table(["fdn_hip.h", "fdn_video.h"], str(tmp_path))[0]) == 77
+    with open(tmp_path / "fdn_video.h", "a") as f:
+        f.write("\nint fdn_chan_stats(int n);\n")
+    with pytest.raises(ValueError, match="fdn_chan_stats"):
+        gen.build_table(["fdn_hip.h", "fdn_video.h"], str(tmp_path))
+
+
+def test_version_mismatch_is_refused(lib, monkeypatch):
+    """a library that answers another version than the table's is refused by name and number, and nothing stays loaded"""
+    import fdn_hip
+    from fdn_hip import _abi
+    monkeypatch.setattr(fdn_hip, "_lib", None)                   # (lib() afresh; the loaded library comes back when the test ends)
+    monkeypatch.setitem(_abi.VERSIONS, "fdn_temporal.h", ("fdn_temporal_abi_version", 7))
+    with pytest.raises(ImportError) as e:
+        fdn_hip.lib()
+    assert str(e.value) == f"{fdn_hip.lib_path()} has temporal ABI version 1, this binding needs 7: rebuild with build.sh"
+    assert fdn_hip._lib is None
+    monkeypatch.setitem(_abi.VERSIONS, "fdn_temporal.h", ("fdn_temporal_abi_version", 1))
+    monkeypatch.setitem(_abi.VERSIONS, "fdn_hip.h", ("fdn_abi_version", 21))
+    with pytest.raises(ImportError, match=r"libfdn_hip\.so has ABI version 22, this binding needs 21: rebuild with build\.sh$"):
+        fdn_hip.lib()
+    assert fdn_hip._lib is None
+
+
+def test_ctypes_prototypes_match_header(lib, gen):
+    """fdn_hip/_abi.py (argtypes of every entry point) holds exactly what include/fdn_hip.h declares, and the loader applied it."""
+    import ctypes as C
+    from fdn_hip._abi import HEADERS, PROTOTYPES
+    assert {n: PROTOTYPES[n] for n in HEADERS["fdn_hip.h"]} == gen.parse_header(os.path.join(ROOT, "include", "fdn_hip.h"))
     assert lib.fdn_fdsa_fused.argtypes is not None and len(lib.fdn_fdsa_fused.argtypes) == len(PROTOTYPES["fdn_fdsa_fused"][1])
     with pytest.raises(C.ArgumentError):
         lib.fdn_fdsa_core(None, None, None, None, 1.5, 38, 32, 32, None)            # a float where an int belongs
@@ -293,18 +353,14 @@ def test_reference_model_registry_is_reached_on_demand(tmp_path):
     assert r.returncode == 0 and "clear error" in r.stdout, r.stderr[-2000:]
 
 
-def test_bench_describes_calls_by_name():
+def test_bench_describes_calls_by_name(gen):
     """bench.py's roofline figures come from the ARGUMENTS of the C-ABI calls it wraps.  They are read by NAME (fdn_hip/_abi.py ARG_NAMES,
     generated from the header), so an inserted or reordered parameter of a later ABI version cannot silently shift a shape: every parser gets
     a call built from the header's own prototype in which each integer parameter carries a distinct value, and the group key it returns must
     show the values of the parameters it names - then the same call with two parameters swapped IN THE TABLE must change the key or raise."""
-    import importlib
     import bench
-    from fdn_hip._abi import ARG_NAMES, PROTOTYPES
-    spec = importlib.util.spec_from_file_location("gen_abi_table", os.path.join(ROOT, "tools", "gen_abi_table.py"))
-    gen = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gen)
-    assert ARG_NAMES == gen.parse_names(os.path.join(ROOT, "include", "fdn_hip.h"))
+    from fdn_hip._abi import ARG_NAMES, HEADERS, PROTOTYPES
+    assert {n: ARG_NAMES[n] for n in HEADERS["fdn_hip.h"]} == gen.parse_names(os.path.join(ROOT, "include", "fdn_hip.h"))
     assert set(ARG_NAMES) == set(PROTOTYPES) and all(len(ARG_NAMES[n]) == len(PROTOTYPES[n][1]) for n in PROTOTYPES)
     # every entry point the step's by_entry_point_ms can name either has a parser or is a helper without a shape figure; the heavy ones must have one
     heavy = ("fdn_conv1x1", "fdn_fdsa_fused", "fdn_fdsa_out", "fdn_fdsa_core", "fdn_fdffn_mid", "fdn_ffn_tail", "fdn_dwconv_gate", "fdn_conv2d",

@@ -4,7 +4,6 @@ include/fdn_lowlight.h (version, prototype table, argument checks before any lau
 are host arithmetic), what fdn_hip.lowlight refuses, and the argument parsing of calculate_lowlight_metrics.py and
 validate_fdn.py --lowlight.  No GPU compute."""
 import ctypes
-import importlib.util
 import os
 
 import numpy as np
@@ -100,25 +99,13 @@ def test_ciede2000_restatement():
 
 
 def test_version_and_prototype_table(lib):
-    """the new header has its own version and table; fdn_hip.h stands at ABI 22 with 74 entry points; no name is shared"""
-    import fdn_hip
-    from fdn_hip import _abi, _abi_ensemble, _abi_lowlight, _abi_spectral, _abi_temporal, _abi_video, _abi_vmetrics
-    assert lib.fdn_lowlight_abi_version() == fdn_hip.LOWLIGHT_ABI_VERSION == 1
-    assert lib.fdn_abi_version() == fdn_hip.ABI_VERSION == 22 and len(_abi.PROTOTYPES) == 74
-    assert lib.fdn_spectral_abi_version() == fdn_hip.SPECTRAL_ABI_VERSION == 1 and len(_abi_spectral.PROTOTYPES) == 5
-    spec = importlib.util.spec_from_file_location("gen_abi_table", os.path.join(ROOT, "tools", "gen_abi_table.py"))
-    gen = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gen)
-    header = os.path.join(ROOT, "include", "fdn_lowlight.h")
-    assert list(_abi_lowlight.PROTOTYPES.items()) == list(gen.parse_header(header).items())
-    assert list(_abi_lowlight.ARG_NAMES.items()) == list(gen.parse_names(header).items())
-    assert list(_abi_lowlight.PROTOTYPES) == NAMES
-    assert _abi_lowlight.PROTOTYPES["fdn_loe_sample_dims"] == ("I", ["I", "I", "I", "P", "P"])
-    assert _abi_lowlight.PROTOTYPES["fdn_loe_ws"] == ("L", ["I"] * 4) and _abi_lowlight.PROTOTYPES["fdn_deltae00_ws"] == ("L", ["I"] * 3)
-    assert _abi_lowlight.PROTOTYPES["fdn_loe_u8"] == _abi_lowlight.PROTOTYPES["fdn_loe_map_u8"] == ("I", ["P", "P", "I", "I", "I", "I", "P", "P", "P"])
-    assert _abi_lowlight.PROTOTYPES["fdn_deltae00_u8"] == ("I", ["P", "P", "I", "I", "I", "I", "P", "P", "P", "P"])
-    for other in (_abi, _abi_video, _abi_temporal, _abi_vmetrics, _abi_ensemble, _abi_spectral):
-        assert not set(_abi_lowlight.PROTOTYPES) & set(other.PROTOTYPES)
+    """the entry points of include/fdn_lowlight.h in the one table (tests/test_host_cpu.py holds it to the headers): names, signatures"""
+    from fdn_hip._abi import HEADERS, PROTOTYPES
+    assert HEADERS["fdn_lowlight.h"] == NAMES
+    assert PROTOTYPES["fdn_loe_sample_dims"] == ("I", ["I", "I", "I", "P", "P"])
+    assert PROTOTYPES["fdn_loe_ws"] == ("L", ["I"] * 4) and PROTOTYPES["fdn_deltae00_ws"] == ("L", ["I"] * 3)
+    assert PROTOTYPES["fdn_loe_u8"] == PROTOTYPES["fdn_loe_map_u8"] == ("I", ["P", "P", "I", "I", "I", "I", "P", "P", "P"])
+    assert PROTOTYPES["fdn_deltae00_u8"] == ("I", ["P", "P", "I", "I", "I", "I", "P", "P", "P", "P"])
     assert lib.fdn_loe_ws.restype == ctypes.c_long and lib.fdn_deltae00_ws.restype == ctypes.c_long
     assert lib.fdn_loe_u8.argtypes == [ctypes.c_void_p] * 2 + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 3
     src = open(os.path.join(ROOT, "fdn-tip2025_amd", "fdn_hip", "lowlight.py")).read()
@@ -252,25 +239,3 @@ def test_validate_fdn_parser_keeps_its_old_command_lines(tmp_path):
     for bad in (["--loe-size", "50"], ["--lowlight", "--loe-size", "-1"], ["--lowlight", "--loe-size", "x"]):
         with pytest.raises(SystemExit):
             validate_fdn.parse_args(base + bad)
-
-
-def test_kernel_table_of_the_dependency():
-    """libfdn_hip.so reaches the new code through its dependency libfdn_lowlight.so, whose code objects tests/kernel_table.txt does not
-    see; tests/kernel_table_lowlight.txt is its table on the same terms: one row per compiled kernel, each with a host stub and a GPU test
-    file that launches it (a kernel trace of that file alone showed all six dispatched).  No kernel sits in both."""
-    import fdn_hip
-    spec = importlib.util.spec_from_file_location("kernel_coverage", os.path.join(ROOT, "tools", "kernel_coverage.py"))
-    cov = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cov)
-    if not os.path.isfile(fdn_hip.lib_path()):
-        entry.build()
-    dep = os.path.join(os.path.dirname(fdn_hip.lib_path()), "libfdn_lowlight.so")
-    compiled = cov.compiled(dep)
-    rows = cov.read_table(os.path.join(ROOT, "tests", "kernel_table_lowlight.txt"))
-    assert set(rows) == set(compiled), (sorted(set(compiled) - set(rows)), sorted(set(rows) - set(compiled)))
-    for k, (dem, stub) in compiled.items():
-        assert stub, f"{dem}: no host code launches it"
-        assert rows[k][0] == dem, k
-        files = rows[k][1].split()
-        assert files and all(f.startswith("test_gpu_") and os.path.isfile(os.path.join(ROOT, "tests", f)) for f in files), (dem, files)
-    assert not set(cov.compiled(fdn_hip.lib_path())) & set(compiled)

@@ -3,7 +3,6 @@ before any launch, the band counts, which are host arithmetic), the restatement 
 amp + pha = total), what fdn_hip.spectral refuses, and the argument parsing of calculate_fourier_metrics.py and validate_fdn.py --fourier.
 No GPU compute."""
 import ctypes
-import importlib.util
 import math
 import os
 
@@ -29,25 +28,13 @@ def lib():
 
 
 def test_version_and_prototype_table(lib):
-    """the new header has its own version and table; the other versions and counts stand; no name is shared"""
-    import fdn_hip
-    from fdn_hip import _abi, _abi_ensemble, _abi_spectral, _abi_temporal, _abi_video, _abi_vmetrics
-    assert lib.fdn_spectral_abi_version() == fdn_hip.SPECTRAL_ABI_VERSION == 1
-    assert lib.fdn_abi_version() == fdn_hip.ABI_VERSION == 22 and len(_abi.PROTOTYPES) == 74
-    assert (len(_abi_video.PROTOTYPES), len(_abi_temporal.PROTOTYPES), len(_abi_vmetrics.PROTOTYPES), len(_abi_ensemble.PROTOTYPES)) == (3, 3, 4, 5)
-    spec = importlib.util.spec_from_file_location("gen_abi_table", os.path.join(ROOT, "tools", "gen_abi_table.py"))
-    gen = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gen)
-    header = os.path.join(ROOT, "include", "fdn_spectral.h")
-    assert list(_abi_spectral.PROTOTYPES.items()) == list(gen.parse_header(header).items())
-    assert list(_abi_spectral.ARG_NAMES.items()) == list(gen.parse_names(header).items())
-    assert list(_abi_spectral.PROTOTYPES) == NAMES
-    assert _abi_spectral.PROTOTYPES["fdn_fft_cols_c2c"] == ("I", ["P", "L", "I", "I", "P"])
-    assert _abi_spectral.PROTOTYPES["fdn_spectrum_band_counts"] == ("I", ["I", "I", "I", "P"])
-    assert _abi_spectral.PROTOTYPES["fdn_spectrum_pair_bands_ws"] == ("L", ["L", "I", "I", "I"])
-    assert _abi_spectral.PROTOTYPES["fdn_spectrum_pair_bands"] == ("I", ["P", "P", "P", "P", "L", "I", "I", "L", "I", "P"])
-    for other in (_abi, _abi_video, _abi_temporal, _abi_vmetrics, _abi_ensemble):
-        assert not set(_abi_spectral.PROTOTYPES) & set(other.PROTOTYPES)
+    """the entry points of include/fdn_spectral.h in the one table (tests/test_host_cpu.py holds it to the headers): names, signatures"""
+    from fdn_hip._abi import HEADERS, PROTOTYPES
+    assert HEADERS["fdn_spectral.h"] == NAMES
+    assert PROTOTYPES["fdn_fft_cols_c2c"] == ("I", ["P", "L", "I", "I", "P"])
+    assert PROTOTYPES["fdn_spectrum_band_counts"] == ("I", ["I", "I", "I", "P"])
+    assert PROTOTYPES["fdn_spectrum_pair_bands_ws"] == ("L", ["L", "I", "I", "I"])
+    assert PROTOTYPES["fdn_spectrum_pair_bands"] == ("I", ["P", "P", "P", "P", "L", "I", "I", "L", "I", "P"])
     assert lib.fdn_spectrum_pair_bands_ws.restype == ctypes.c_long
     assert lib.fdn_spectrum_pair_bands.argtypes == [ctypes.c_void_p] * 4 + [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_int,
                                                     ctypes.c_void_p]

@@ -2,7 +2,6 @@
 checks before any launch), the restatement of tests/temporal_ref.py judged on its own, the checks fdn_hip.temporal.RatioFilter and
 fdn_hip.harness.enhance_yuv420(temporal=...) make before anything runs, and the two flags of inference_fdn_video.py.  No GPU compute."""
 import ctypes
-import importlib.util
 import os
 
 import numpy as np
@@ -25,22 +24,12 @@ def lib():
 
 
 def test_version_and_prototype_table(lib):
-    """the temporal header has its own version and table; the tables of the three headers share no name"""
-    import fdn_hip
-    from fdn_hip import _abi, _abi_temporal, _abi_video
-    assert lib.fdn_temporal_abi_version() == fdn_hip.TEMPORAL_ABI_VERSION == 1
-    spec = importlib.util.spec_from_file_location("gen_abi_table", os.path.join(ROOT, "tools", "gen_abi_table.py"))
-    gen = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gen)
+    """the entry points of include/fdn_temporal.h in the one table (tests/test_host_cpu.py holds it to the headers): names, signatures"""
+    from fdn_hip._abi import HEADERS, PROTOTYPES
     header = os.path.join(ROOT, "include", "fdn_temporal.h")
-    assert list(_abi_temporal.PROTOTYPES.items()) == list(gen.parse_header(header).items())
-    assert list(_abi_temporal.ARG_NAMES.items()) == list(gen.parse_names(header).items())
-    assert list(_abi_temporal.PROTOTYPES) == NAMES
-    assert _abi_temporal.PROTOTYPES["fdn_luma_hist"] == ("I", ["P", "P", "I", "I", "I", "I", "P"])
-    assert _abi_temporal.PROTOTYPES["fdn_ratio_smooth"] == ("I", ["P", "P", "P", "F", "I", "I", "P", "P", "P", "P"])
-    assert not set(_abi_temporal.PROTOTYPES) & set(_abi.PROTOTYPES)
-    assert not set(_abi_temporal.PROTOTYPES) & set(_abi_video.PROTOTYPES)
-    assert not set(_abi_video.PROTOTYPES) & set(_abi.PROTOTYPES)
+    assert HEADERS["fdn_temporal.h"] == NAMES
+    assert PROTOTYPES["fdn_luma_hist"] == ("I", ["P", "P", "I", "I", "I", "I", "P"])
+    assert PROTOTYPES["fdn_ratio_smooth"] == ("I", ["P", "P", "P", "F", "I", "I", "P", "P", "P", "P"])
     assert lib.fdn_ratio_smooth.argtypes == [ctypes.c_void_p] * 3 + [ctypes.c_float, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 4
     assert "#define FDN_TEMPORAL_STATE_WORDS 258" in open(header).read()
     from fdn_hip import temporal

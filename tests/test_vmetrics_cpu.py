@@ -3,7 +3,6 @@ any launch), the restatement of tests/vmetrics_ref.py judged on its own (its SSI
 hand), the host arithmetic of fdn_hip.video_metrics and of VideoScore on synthetic integer sums and histograms, and what
 calculate_video_metrics.py refuses before it touches a device.  No GPU compute."""
 import ctypes
-import importlib.util
 import math
 import os
 import subprocess
@@ -31,25 +30,12 @@ def lib():
 
 
 def test_versions_and_prototype_table(lib):
-    """the new header has its own version and table; the other three versions and counts stand; the four tables share no name"""
-    import fdn_hip
-    from fdn_hip import _abi, _abi_temporal, _abi_video, _abi_vmetrics
-    assert lib.fdn_vmetrics_abi_version() == fdn_hip.VMETRICS_ABI_VERSION == 1
-    assert lib.fdn_abi_version() == fdn_hip.ABI_VERSION == 22 and len(_abi.PROTOTYPES) == 74
-    assert lib.fdn_video_abi_version() == fdn_hip.VIDEO_ABI_VERSION == 1 and len(_abi_video.PROTOTYPES) == 3
-    assert lib.fdn_temporal_abi_version() == fdn_hip.TEMPORAL_ABI_VERSION == 1 and len(_abi_temporal.PROTOTYPES) == 3
-    spec = importlib.util.spec_from_file_location("gen_abi_table", os.path.join(ROOT, "tools", "gen_abi_table.py"))
-    gen = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gen)
-    header = os.path.join(ROOT, "include", "fdn_vmetrics.h")
-    assert list(_abi_vmetrics.PROTOTYPES.items()) == list(gen.parse_header(header).items())
-    assert list(_abi_vmetrics.ARG_NAMES.items()) == list(gen.parse_names(header).items())
-    assert list(_abi_vmetrics.PROTOTYPES) == NAMES
-    assert _abi_vmetrics.PROTOTYPES["fdn_yuv420_pair_stats"] == ("I", ["P", "P", "P", "I", "I", "I", "I", "I", "P"])
-    assert _abi_vmetrics.PROTOTYPES["fdn_yuv420_ssim_y_ws"] == ("L", ["I", "I", "I"])
-    assert _abi_vmetrics.PROTOTYPES["fdn_yuv420_ssim_y"] == ("I", ["P", "P", "P", "P", "P", "I", "I", "I", "I", "P"])
-    for other in (_abi, _abi_video, _abi_temporal):
-        assert not set(_abi_vmetrics.PROTOTYPES) & set(other.PROTOTYPES)
+    """the entry points of include/fdn_vmetrics.h in the one table (tests/test_host_cpu.py holds it to the headers): names, signatures"""
+    from fdn_hip._abi import HEADERS, PROTOTYPES
+    assert HEADERS["fdn_vmetrics.h"] == NAMES
+    assert PROTOTYPES["fdn_yuv420_pair_stats"] == ("I", ["P", "P", "P", "I", "I", "I", "I", "I", "P"])
+    assert PROTOTYPES["fdn_yuv420_ssim_y_ws"] == ("L", ["I", "I", "I"])
+    assert PROTOTYPES["fdn_yuv420_ssim_y"] == ("I", ["P", "P", "P", "P", "P", "I", "I", "I", "I", "P"])
     assert lib.fdn_yuv420_ssim_y_ws.restype == ctypes.c_long and lib.fdn_yuv420_ssim_y_ws.argtypes == [ctypes.c_int] * 3
     assert lib.fdn_yuv420_pair_stats.argtypes == [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p]
 
