@@ -259,7 +259,7 @@ def enhance_frame_tiled(net, lpnet, img_u8, tile, bgr=True, ratio_mode="lolblur"
 
 @torch.no_grad()
 def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=True, tile=None, ratio_from="frame", overlap=0, batch=8,
-                blend="average", ensemble=1):
+                blend="average", ensemble=1, correct=None):
     """One validation step of the reference (image_restoration_model.py:578-586, :650-658, :746-748, :844-848) for a batch, on the device:
     uint8 low-quality and ground-truth frames [B,h,w,3] -> (uint8 result [B,h,w,3], PSNR list, SSIM list, ratio [B,1]).
     ratio_mode: "gt" feeds mean(gray(lq)) / mean(gray(gt)) as the validation does (gt_ratio; lpnet is not used and may be None),
@@ -267,10 +267,21 @@ def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=Tr
     (img1) against gt_u8, as the reference scores tensor2img's images (fdn_hip.metrics.calculate_psnr_ssim_u8).  Eager forward on the
     caller's stream.
     tile / ratio_from / overlap / batch / blend as in enhance_u8; ratio_from "tile" is the reference's val.grids validation.  With a tile
-    the returned ratio is [B,T,1], one row per tile.  ensemble as in enhance_u8: the same ratio, the averaged result scored."""
+    the returned ratio is [B,T,1], one row per tile.  ensemble as in enhance_u8: the same ratio, the averaged result scored.
+    correct: None, or "gt_mean" / "mean_var": two more values are returned, the PSNR list and the SSIM list of the result after that
+    brightness correction towards gt_u8 (fdn_hip.correct.calculate_psnr_ssim_corrected_u8); the first four are what they are without."""
     from .ensemble import check_ensemble
     from .metrics import calculate_psnr_ssim_u8
     from .tiling import check_blend
+    if correct is not None:
+        from .correct import calculate_psnr_ssim_corrected_u8, check_mode
+        check_mode(correct)
+
+    def scored(out, ratio):
+        psnr, ssim = calculate_psnr_ssim_u8(out, gt_u8, crop_border=crop_border, bgr=bgr)
+        if correct is None:
+            return out, psnr, ssim, ratio
+        return (out, psnr, ssim, ratio) + tuple(calculate_psnr_ssim_corrected_u8(gt_u8, out, correct, crop_border=crop_border, bgr=bgr))
     if ratio_mode not in ("gt", "lolblur", "lolv1"):
         raise ValueError(f"ratio_mode {ratio_mode!r}")
     check_blend(blend)
@@ -286,9 +297,7 @@ def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=Tr
     if tile is not None and lq_u8.dim() == 4 and resolve_tile(tile, lq_u8.shape[1], lq_u8.shape[2]) is not None:
         done = [enhance_frame_tiled(net, lpnet, lq_u8[b], tile, bgr=bgr, ratio_mode=ratio_mode, ratio_from=ratio_from, gt_u8=gt_u8[b],
                                     overlap=overlap, batch=batch, blend=blend, ensemble=ensemble) for b in range(lq_u8.shape[0])]
-        out = torch.stack([o for o, _ in done])
-        psnr, ssim = calculate_psnr_ssim_u8(out, gt_u8, crop_border=crop_border, bgr=bgr)
-        return out, psnr, ssim, torch.stack([r for _, r in done])
+        return scored(torch.stack([o for o, _ in done]), torch.stack([r for _, r in done]))
     x, h, w = preprocess(lq_u8, bgr=bgr)
     if ratio_mode == "gt":
         ratio = gt_ratio(x, preprocess(gt_u8, bgr=bgr)[0])
@@ -301,8 +310,7 @@ def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=Tr
         out = _ensemble_u8(net, lq_u8, ratio, ensemble, batch, h, w, bgr)
     else:
         out = postprocess(net(x, ratio_i=ratio, device=x.device)[0].contiguous(), h, w, bgr=bgr)
-    psnr, ssim = calculate_psnr_ssim_u8(out, gt_u8, crop_border=crop_border, bgr=bgr)
-    return out, psnr, ssim, ratio
+    return scored(out, ratio)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -21,7 +21,10 @@ line and to the csv (calculate_fourier_metrics.py has what they mean): the ampli
 8-bit frame (no crop_border; the width must be even), the reference's FFTLoss, and per band the columns of that tool's csv.  --lowlight appends the two low-light scores of fdn_hip.lowlight
 (calculate_lowlight_metrics.py has what they mean): loe, the lightness order error of the input frame against the restored one on a grid of
 --loe-size points along the short side (0: every pixel), and deltae, the mean CIEDE2000 difference of the restored frame against the
-ground truth, both from the whole 8-bit frames the driver holds on the GPU anyway.
+ground truth, both from the whole 8-bit frames the driver holds on the GPU anyway.  --correct gt_mean|mean_var prints, beside the plain
+scores, the PSNR and SSIM of the restored frame after that brightness correction towards the ground truth (calculate_psnr_ssim.py has
+what the two mean): a wrong ratio costs the plain scores and not these.  A frame without a correction scores nan there; it is named on
+stderr and the exit status is 1.
 """
 import argparse
 import glob
@@ -77,6 +80,8 @@ def parse_args(argv=None):
     ap.add_argument("--lowlight", action="store_true", default=argparse.SUPPRESS,
                     help="also score the lightness order error against the input and the CIEDE2000 difference against the ground truth")
     ap.add_argument("--loe-size", type=int, default=argparse.SUPPRESS, help="with --lowlight: points along the short side of LOE's sample grid (default 50; 0 = full resolution)")
+    ap.add_argument("--correct", choices=("gt_mean", "mean_var"), default=argparse.SUPPRESS,
+                    help="also score every frame after a brightness correction towards the ground truth (fdn_hip.correct)")
     a = ap.parse_args(argv)
     if not 1 <= a.fourier_bands <= 32:
         ap.error("--fourier-bands must be in 1 .. 32")
@@ -94,6 +99,15 @@ def parse_args(argv=None):
     except ValueError as e:
         ap.error(str(e))
     return a
+
+
+def csv_header(a):
+    """the first line of --csv: columns are added only by the flags that are given"""
+    cols = "frame,psnr,ssim,ratio"
+    if a.fourier:
+        from fdn_hip import spectral
+        cols += "," + ",".join(spectral.csv_header(a.fourier_bands))
+    return cols + (",loe,deltae" if getattr(a, "lowlight", False) else "") + (",psnr_corr,ssim_corr" if getattr(a, "correct", None) else "")
 
 
 def main(argv=None):
@@ -116,6 +130,8 @@ def main(argv=None):
         from calculate_lowlight_metrics import lowlight_line
         from fdn_hip import FdnHipError, lowlight
 
+    mode_corr = getattr(a, "correct", None)
+
     dev = torch.device(a.device)
     torch.cuda.set_device(dev)
     net = Net().to(dev).eval()
@@ -127,16 +143,16 @@ def main(argv=None):
     mode = RATIO_MODE[(a.ratio, a.variant)]
 
     n = len(a.pairs)
-    psnr, ssim, ratio, fourier, ll = [None] * n, [None] * n, [None] * n, [None] * n, [None] * n
+    psnr, ssim, ratio, fourier, ll, corr = [None] * n, [None] * n, [None] * n, [None] * n, [None] * n, [None] * n
     with ThreadPoolExecutor(max_workers=4) as pool:
         writers = []
         for idx, lqs, gts in decoded_groups(a.pairs, a.batch, pool):
             lq, gt = torch.from_numpy(lqs).to(dev), torch.from_numpy(gts).to(dev)
             hint_large_frame(a.tile, lqs.shape[1], lqs.shape[2])
             hint_hard_seam(a.tile, a.tile_blend, a.tile_overlap, lqs.shape[1], lqs.shape[2])
-            out, p, s, r = validate_u8(net, lp, lq, gt, ratio_mode=mode, crop_border=a.crop_border, bgr=False, tile=a.tile,
-                                       ratio_from=a.tile_ratio, overlap=a.tile_overlap, batch=a.batch, blend=a.tile_blend,
-                                       ensemble=a.ensemble)
+            out, p, s, r, *pc = validate_u8(net, lp, lq, gt, ratio_mode=mode, crop_border=a.crop_border, bgr=False, tile=a.tile,
+                                            ratio_from=a.tile_ratio, overlap=a.tile_overlap, batch=a.batch, blend=a.tile_blend,
+                                            ensemble=a.ensemble, **({"correct": mode_corr} if mode_corr else {}))
             r = r.reshape(r.shape[0], -1).cpu().tolist()              # one ratio per frame, or one per tile of a tiled frame
             frames = out.cpu().numpy() if a.dest else None
             if a.fourier:
@@ -155,6 +171,8 @@ def main(argv=None):
                     fourier[i] = fm[k]
                 if want_ll:
                     ll[i] = lm[k]
+                if mode_corr:
+                    corr[i] = (pc[0][k], pc[1][k])
                 if a.dest:
                     writers.append(pool.submit(write_rgb, a.dest[i], frames[k]))
         for w in writers:
@@ -163,20 +181,28 @@ def main(argv=None):
         basename = os.path.splitext(os.path.basename(lq_path))[0]
         tail = f", \t{fourier_line(fourier[i])}" if a.fourier else ""
         tail += f", \t{lowlight_line(ll[i])}" if want_ll else ""
+        tail += f", \t{mode_corr} PSNR: {corr[i][0]:.6f} dB, \t{mode_corr} SSIM: {corr[i][1]:.6f}" if mode_corr else ""
         print(f'{i+1:3d}: {basename:25}. \tPSNR: {psnr[i]:.6f} dB, \tSSIM: {ssim[i]:.6f}{tail}')
     tail = ", " + fourier_line({k: mean_of([m[k] for m in fourier]) for k in SUMMARY_KEYS}) if a.fourier else ""
     tail += ", " + lowlight_line({k: sum(m[k] for m in ll) / n for k in ("loe", "deltae")}) if want_ll else ""
+    tail += f", {mode_corr} PSNR: {sum(c[0] for c in corr) / n:.6f} dB, {mode_corr} SSIM: {sum(c[1] for c in corr) / n:.6f}" if mode_corr else ""
     print(f'Average: PSNR: {sum(psnr) / n:.6f} dB, SSIM: {sum(ssim) / n:.6f}{tail}')
     if a.csv:
         os.makedirs(os.path.dirname(a.csv) or ".", exist_ok=True)
         with open(a.csv, "w") as f:
-            f.write("frame,psnr,ssim,ratio" + ("," + ",".join(spectral.csv_header(a.fourier_bands)) if a.fourier else "") + (",loe,deltae" if want_ll else "") + "\n")
+            f.write(csv_header(a) + "\n")
             for i, ((lq_path, _), p, s, r) in enumerate(zip(a.pairs, psnr, ssim, ratio)):
                 tail = "," + ",".join(spectral.csv_row(fourier[i])) if a.fourier else ""
                 tail += f",{ll[i]['loe']!r},{ll[i]['deltae']!r}" if want_ll else ""
+                tail += f",{corr[i][0]!r},{corr[i][1]!r}" if mode_corr else ""
                 f.write(f"{lq_path},{p!r},{s!r},{';'.join(repr(v) for v in r)}{tail}\n")
     if a.dest:
         print(f"{n} frames -> {a.output}")
+    bad = [lq_path for (lq_path, _), c in zip(a.pairs, corr) if mode_corr and (c[0] != c[0] or c[1] != c[1])]
+    for path in bad:
+        print(f"validate_fdn.py: --correct {mode_corr}: the restored {path} has no correction (a flat channel or a black image): nan", file=sys.stderr)
+    if bad:
+        sys.exit(1)
 
 
 if __name__ == "__main__":
