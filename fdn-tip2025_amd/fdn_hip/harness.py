@@ -259,7 +259,7 @@ def enhance_frame_tiled(net, lpnet, img_u8, tile, bgr=True, ratio_mode="lolblur"
 
 @torch.no_grad()
 def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=True, tile=None, ratio_from="frame", overlap=0, batch=8,
-                blend="average", ensemble=1, correct=None):
+                blend="average", ensemble=1, correct=None, sharpness=False):
     """One validation step of the reference (image_restoration_model.py:578-586, :650-658, :746-748, :844-848) for a batch, on the device:
     uint8 low-quality and ground-truth frames [B,h,w,3] -> (uint8 result [B,h,w,3], PSNR list, SSIM list, ratio [B,1]).
     ratio_mode: "gt" feeds mean(gray(lq)) / mean(gray(gt)) as the validation does (gt_ratio; lpnet is not used and may be None),
@@ -269,7 +269,9 @@ def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=Tr
     tile / ratio_from / overlap / batch / blend as in enhance_u8; ratio_from "tile" is the reference's val.grids validation.  With a tile
     the returned ratio is [B,T,1], one row per tile.  ensemble as in enhance_u8: the same ratio, the averaged result scored.
     correct: None, or "gt_mean" / "mean_var": two more values are returned, the PSNR list and the SSIM list of the result after that
-    brightness correction towards gt_u8 (fdn_hip.correct.calculate_psnr_ssim_corrected_u8); the first four are what they are without."""
+    brightness correction towards gt_u8 (fdn_hip.correct.calculate_psnr_ssim_corrected_u8); the first four are what they are without.
+    sharpness: True appends one more value after those, the list of fdn_hip.sharpness.sharpness_metrics(gt_u8, result): per frame the
+    edge error, GMSD and the mean gradients with their ratio."""
     from .ensemble import check_ensemble
     from .metrics import calculate_psnr_ssim_u8
     from .tiling import check_blend
@@ -279,9 +281,13 @@ def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=Tr
 
     def scored(out, ratio):
         psnr, ssim = calculate_psnr_ssim_u8(out, gt_u8, crop_border=crop_border, bgr=bgr)
-        if correct is None:
-            return out, psnr, ssim, ratio
-        return (out, psnr, ssim, ratio) + tuple(calculate_psnr_ssim_corrected_u8(gt_u8, out, correct, crop_border=crop_border, bgr=bgr))
+        res = (out, psnr, ssim, ratio)
+        if correct is not None:
+            res += tuple(calculate_psnr_ssim_corrected_u8(gt_u8, out, correct, crop_border=crop_border, bgr=bgr))
+        if sharpness:
+            from .sharpness import sharpness_metrics
+            res += (sharpness_metrics(gt_u8, out, bgr=bgr),)
+        return res
     if ratio_mode not in ("gt", "lolblur", "lolv1"):
         raise ValueError(f"ratio_mode {ratio_mode!r}")
     check_blend(blend)

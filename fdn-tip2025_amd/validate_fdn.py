@@ -24,7 +24,9 @@ line and to the csv (calculate_fourier_metrics.py has what they mean): the ampli
 ground truth, both from the whole 8-bit frames the driver holds on the GPU anyway.  --correct gt_mean|mean_var prints, beside the plain
 scores, the PSNR and SSIM of the restored frame after that brightness correction towards the ground truth (calculate_psnr_ssim.py has
 what the two mean): a wrong ratio costs the plain scores and not these.  A frame without a correction scores nan there; it is named on
-stderr and the exit status is 1.
+stderr and the exit status is 1.  --sharpness appends the three deblurring figures of fdn_hip.sharpness (calculate_sharpness_metrics.py has what
+they mean): edge, the reference's EdgeLoss of the restored frame against the ground truth, gmsd, and grad_ratio, the mean gradient
+magnitude of the restored frame over that of the ground truth (below 1: softer than the truth), from the whole 8-bit frames.
 """
 import argparse
 import glob
@@ -82,6 +84,8 @@ def parse_args(argv=None):
     ap.add_argument("--loe-size", type=int, default=argparse.SUPPRESS, help="with --lowlight: points along the short side of LOE's sample grid (default 50; 0 = full resolution)")
     ap.add_argument("--correct", choices=("gt_mean", "mean_var"), default=argparse.SUPPRESS,
                     help="also score every frame after a brightness correction towards the ground truth (fdn_hip.correct)")
+    ap.add_argument("--sharpness", action="store_true", default=argparse.SUPPRESS,
+                    help="also score the edge error, GMSD and the mean-gradient ratio against the ground truth (fdn_hip.sharpness)")
     a = ap.parse_args(argv)
     if not 1 <= a.fourier_bands <= 32:
         ap.error("--fourier-bands must be in 1 .. 32")
@@ -107,7 +111,8 @@ def csv_header(a):
     if a.fourier:
         from fdn_hip import spectral
         cols += "," + ",".join(spectral.csv_header(a.fourier_bands))
-    return cols + (",loe,deltae" if getattr(a, "lowlight", False) else "") + (",psnr_corr,ssim_corr" if getattr(a, "correct", None) else "")
+    return cols + (",loe,deltae" if getattr(a, "lowlight", False) else "") + (",psnr_corr,ssim_corr" if getattr(a, "correct", None) else "") + (
+        ",edge,gmsd,grad_ratio" if getattr(a, "sharpness", False) else "")
 
 
 def main(argv=None):
@@ -131,6 +136,10 @@ def main(argv=None):
         from fdn_hip import FdnHipError, lowlight
 
     mode_corr = getattr(a, "correct", None)
+    want_sh = getattr(a, "sharpness", False)
+    if want_sh:
+        from calculate_sharpness_metrics import sharpness_line
+        from fdn_hip import FdnHipError, sharpness
 
     dev = torch.device(a.device)
     torch.cuda.set_device(dev)
@@ -143,7 +152,7 @@ def main(argv=None):
     mode = RATIO_MODE[(a.ratio, a.variant)]
 
     n = len(a.pairs)
-    psnr, ssim, ratio, fourier, ll, corr = [None] * n, [None] * n, [None] * n, [None] * n, [None] * n, [None] * n
+    psnr, ssim, ratio, fourier, ll, corr, sh = [None] * n, [None] * n, [None] * n, [None] * n, [None] * n, [None] * n, [None] * n
     with ThreadPoolExecutor(max_workers=4) as pool:
         writers = []
         for idx, lqs, gts in decoded_groups(a.pairs, a.batch, pool):
@@ -165,6 +174,11 @@ def main(argv=None):
                     lm = lowlight.lowlight_metrics(lq, out, gt, size=loe_size, bgr=False)
                 except FdnHipError as e:
                     sys.exit(f"validate_fdn.py: --lowlight: {e}")
+            if want_sh:
+                try:
+                    sm = sharpness.sharpness_metrics(gt, out, bgr=False)
+                except FdnHipError as e:
+                    sys.exit(f"validate_fdn.py: --sharpness: {e}")
             for k, i in enumerate(idx):
                 psnr[i], ssim[i], ratio[i] = p[k], s[k], r[k]
                 if a.fourier:
@@ -173,6 +187,8 @@ def main(argv=None):
                     ll[i] = lm[k]
                 if mode_corr:
                     corr[i] = (pc[0][k], pc[1][k])
+                if want_sh:
+                    sh[i] = sm[k]
                 if a.dest:
                     writers.append(pool.submit(write_rgb, a.dest[i], frames[k]))
         for w in writers:
@@ -182,10 +198,12 @@ def main(argv=None):
         tail = f", \t{fourier_line(fourier[i])}" if a.fourier else ""
         tail += f", \t{lowlight_line(ll[i])}" if want_ll else ""
         tail += f", \t{mode_corr} PSNR: {corr[i][0]:.6f} dB, \t{mode_corr} SSIM: {corr[i][1]:.6f}" if mode_corr else ""
+        tail += f", \t{sharpness_line(sh[i])}" if want_sh else ""
         print(f'{i+1:3d}: {basename:25}. \tPSNR: {psnr[i]:.6f} dB, \tSSIM: {ssim[i]:.6f}{tail}')
     tail = ", " + fourier_line({k: mean_of([m[k] for m in fourier]) for k in SUMMARY_KEYS}) if a.fourier else ""
     tail += ", " + lowlight_line({k: sum(m[k] for m in ll) / n for k in ("loe", "deltae")}) if want_ll else ""
     tail += f", {mode_corr} PSNR: {sum(c[0] for c in corr) / n:.6f} dB, {mode_corr} SSIM: {sum(c[1] for c in corr) / n:.6f}" if mode_corr else ""
+    tail += ", " + sharpness_line({k: sum(m[k] for m in sh) / n for k in ("edge", "gmsd", "grad_ratio")}) if want_sh else ""
     print(f'Average: PSNR: {sum(psnr) / n:.6f} dB, SSIM: {sum(ssim) / n:.6f}{tail}')
     if a.csv:
         os.makedirs(os.path.dirname(a.csv) or ".", exist_ok=True)
@@ -195,6 +213,7 @@ def main(argv=None):
                 tail = "," + ",".join(spectral.csv_row(fourier[i])) if a.fourier else ""
                 tail += f",{ll[i]['loe']!r},{ll[i]['deltae']!r}" if want_ll else ""
                 tail += f",{corr[i][0]!r},{corr[i][1]!r}" if mode_corr else ""
+                tail += f",{sh[i]['edge']!r},{sh[i]['gmsd']!r},{sh[i]['grad_ratio']!r}" if want_sh else ""
                 f.write(f"{lq_path},{p!r},{s!r},{';'.join(repr(v) for v in r)}{tail}\n")
     if a.dest:
         print(f"{n} frames -> {a.output}")
