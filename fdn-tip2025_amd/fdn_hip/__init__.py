@@ -71,7 +71,7 @@ def _declare(l, missing_ok=False, protos=PROTOTYPES):
     """argtypes / restype of every entry point (a wrong argument count or kind raises here instead of corrupting the call).
     missing_ok: skip the entry points `l` lacks (tools/ab_libs.py loads builds of an older ABI beside this one).
     protos: the table of another library of this package (fdn_hip.correct declares libfdn_correct.so with its own)."""
-    kinds = {"P": ctypes.c_void_p, "I": ctypes.c_int, "L": ctypes.c_long, "F": ctypes.c_float, "DESC": ctypes.POINTER(Conv1x1Desc)}
+    kinds = {"P": ctypes.c_void_p, "I": ctypes.c_int, "L": ctypes.c_long, "F": ctypes.c_float, "D": ctypes.c_double, "DESC": ctypes.POINTER(Conv1x1Desc)}
     for name, (ret, sig) in protos.items():
         f = getattr(l, name, None) if missing_ok else getattr(l, name)      # AttributeError: the library lacks a symbol the header declares
         if f is None:

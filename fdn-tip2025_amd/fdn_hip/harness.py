@@ -27,6 +27,10 @@ the ratio across the frames of a stream (fdn_hip.temporal, include/fdn_temporal.
 ensemble = 2, 4 or 8 (enhance_u8, validate_u8, enhance_frame_tiled; no reference counterpart) is the geometric self-ensemble of
 fdn_hip.ensemble: FDN runs on that many flipped / transposed copies of each frame - or, tiled, of each tile - with the ratio of the
 untransformed frame or tile, and the results, mapped back, are averaged.  ensemble = 1 is the code path without the keyword.
+
+bracket = a tuple of exposure stops (enhance_u8, validate_u8, enhance_frame_tiled; no reference counterpart) renders every frame at the
+ratios fdn_hip.fusion.bracket_ratios makes of the one the call without a bracket would feed, and fuses the renderings into one locally
+exposed frame (fdn_hip.fusion, render_ratios).  bracket = None is the code path without the keyword.
 """
 import ctypes
 from dataclasses import dataclass
@@ -187,7 +191,7 @@ def _forward(net, lpnet, x, ratio_mode, ratio):
 
 @torch.no_grad()
 def enhance_u8(net, lpnet, img_u8, bgr=True, ratio_mode="lolblur", ratio=None, tile=None, ratio_from="frame", overlap=0, batch=8,
-               blend="average", ensemble=1):
+               blend="average", ensemble=1, bracket=None, fusion=(1, 1, 1)):
     """uint8 in -> uint8 out through LPNet -> FDN (the body of the reference's per-image loop, batched).
     ratio_mode: "lolblur" feeds LPNet's prediction (inference_fdn_lolblur.py:69-71), "lolv1" feeds
     mean(gray)/prediction (inference_fdn_lolv1.py:57-62), "fixed" feeds the caller's `ratio` [B,1] and skips LPNet - the
@@ -197,13 +201,21 @@ def enhance_u8(net, lpnet, img_u8, bgr=True, ratio_mode="lolblur", ratio=None, t
     `overlap` pixels, the ratio taken from the whole frame or per tile (ratio_from, see tile_ratio; "fixed" then also takes [B,T,1]),
     the tiles merged by the reference's average or feathered (blend, see tiling.merge).  Without a tile, blend does nothing.
     ensemble: 1, 2, 4 or 8 copies of every frame (of every tile, with a tile) through FDN, averaged (fdn_hip.ensemble); the ratio is the
-    one the call without `ensemble` feeds, taken once from the untransformed frame, and the forwards are eager, `batch` samples each."""
+    one the call without `ensemble` feeds, taken once from the untransformed frame, and the forwards are eager, `batch` samples each.
+    bracket: None, or 1 to 16 exposure stops, for example (-1, 0, 1): every frame is rendered at the ratios
+    fdn_hip.fusion.bracket_ratios makes of the one the call without a bracket feeds (ratio * 2^-stop: a positive stop is brighter), `batch`
+    stops per eager forward, and the renderings are fused over [:h, :w] (fdn_hip.fusion.fuse) before postprocess.  With a tile every stop
+    is the merged fp32 frame of the tiled route, with an ensemble its fp32 mean.  fusion: the exponents of contrast, saturation and
+    well-exposedness in the fusion's weights."""
     from .ensemble import check_ensemble
     from .tiling import check_blend
     if ratio_mode not in ("lolblur", "lolv1", "fixed"):
         raise ValueError(f"ratio_mode {ratio_mode!r}")
     check_blend(blend)
     check_ensemble(ensemble)
+    if bracket is not None:
+        from .fusion import check_bracket, check_exponents
+        bracket, fusion = check_bracket(bracket), check_exponents(fusion)
     if img_u8.dim() == 3:
         img_u8 = img_u8.unsqueeze(0)
     if tile is not None and img_u8.dim() == 4 and resolve_tile(tile, img_u8.shape[1], img_u8.shape[2]) is not None:
@@ -211,8 +223,15 @@ def enhance_u8(net, lpnet, img_u8, bgr=True, ratio_mode="lolblur", ratio=None, t
             raise FdnHipError(f"ratio_mode 'fixed' needs ratio [B,1] or [B,T,1] for B = {img_u8.shape[0]}")
         return torch.stack([enhance_frame_tiled(net, lpnet, img_u8[b], tile, bgr=bgr, ratio_mode=ratio_mode, ratio_from=ratio_from,
                                                 ratio=None if ratio is None else ratio[b].reshape(-1, 1), overlap=overlap, batch=batch,
-                                                blend=blend, ensemble=ensemble)[0]
+                                                blend=blend, ensemble=ensemble, bracket=bracket, fusion=fusion)[0]
                             for b in range(img_u8.shape[0])])
+    if bracket is not None:
+        if ratio_mode == "fixed":
+            if ratio is None or tuple(ratio.shape) != (img_u8.shape[0], 1):
+                raise FdnHipError(f"ratio_mode 'fixed' needs ratio [B,1] for B = {img_u8.shape[0]}")
+        else:
+            ratio = frame_ratio(lpnet, preprocess(img_u8, bgr=bgr)[0], ratio_mode)
+        return _bracket_u8(net, img_u8, ratio.to(device=img_u8.device), bracket, fusion, batch, ensemble, bgr)
     if ensemble != 1:
         if ratio_mode == "fixed":
             if ratio is None or tuple(ratio.shape) != (img_u8.shape[0], 1):
@@ -232,14 +251,72 @@ def _ensemble_u8(net, img_u8, ratio, ensemble, batch, h, w, bgr):
 
 
 @torch.no_grad()
+def render_ratios(net, img_u8, ratios, bgr=True, tile=None, overlap=0, batch=8, blend="average", ensemble=1, run=None, split=None):
+    """One uint8 frame [h,w,3] through FDN at K ratios -> (fp32 [K,3,H,W], h, w) with H >= h, W >= w: the K renderings
+    fdn_hip.fusion.fuse takes.  ratios: [K,1], or with a tile also [K,T,1], one row per tile.
+    Untiled: the reflect-padded frame repeated, `batch` ratios per eager forward through the fixed-ratio route; the results keep their
+    padding.  ensemble 2, 4 or 8: every rendering is the fp32 mean of that many copies (fdn_hip.ensemble.mean), h x w.
+    tile (crop_h, crop_w): every rendering is the merged fp32 frame of the tiled route (tiling.run_tiles, or the caller's run(tiles, ratio)
+    as enhance_frame_tiled takes it, then tiling.merge with `blend`), h x w.  split: the (tiles, origins) of tiling.split_u8 where the
+    caller holds them already."""
+    from . import tiling
+    if img_u8.dim() != 3 or img_u8.shape[-1] != 3:
+        raise FdnHipError(f"expected one uint8 frame [h,w,3], got {tuple(img_u8.shape)}")
+    if batch < 1:
+        raise FdnHipError(f"batch must be at least 1, got {batch}")
+    h, w, _ = img_u8.shape
+    K = ratios.shape[0]
+    ratios = ratios.to(device=img_u8.device, dtype=torch.float32)
+    if tile is not None:
+        tiles, ij = split if split is not None else tiling.split_u8(img_u8, tile[0], tile[1], bgr=bgr, overlap=overlap)
+        T = tiles.shape[0]
+        if ratios.dim() == 2:
+            ratios = ratios.reshape(K, 1, 1).expand(K, T, 1)
+        if tuple(ratios.shape) != (K, T, 1):
+            raise FdnHipError(f"render_ratios on {T} tiles needs ratios [K,1] or [K,{T},1], got {tuple(ratios.shape)}")
+        frames = []
+        for k in range(K):
+            r = ratios[k].contiguous()
+            outs = tiling.run_tiles(net, tiles, r, batch, ensemble=ensemble) if run is None else run(tiles, r)
+            frames.append(tiling.merge(outs, ij, h, w, blend))
+        return torch.cat(frames), h, w
+    if ratios.dim() != 2 or ratios.shape[1] != 1:
+        raise FdnHipError(f"render_ratios needs ratios [K,1], got {tuple(ratios.shape)}")
+    if ensemble != 1:
+        from . import ensemble as ens
+        one = img_u8.unsqueeze(0)
+        return torch.cat([ens.mean(*ens.forward_ensemble(net, one, ratios[k:k + 1], ensemble, batch, bgr=bgr), h, w) for k in range(K)]), h, w
+    x = preprocess(img_u8, bgr=bgr)[0]
+    frames = torch.empty((K,) + tuple(x.shape[1:]), device=x.device, dtype=torch.float32)
+    for s in range(0, K, batch):
+        n = min(batch, K - s)
+        frames[s:s + n] = _forward(net, None, x.expand(n, -1, -1, -1).contiguous(), "fixed", ratios[s:s + n])
+    return frames, h, w
+
+
+def _bracket_u8(net, img_u8, ratio, bracket, fusion, batch, ensemble, bgr):
+    """uint8 frames [B,h,w,3] + the ratio [B,1] the call without a bracket feeds -> uint8 [B,h,w,3]: frame by frame render_ratios at
+    bracket_ratios of it, fusion.fuse, postprocess"""
+    from . import fusion as fu
+    rs = fu.bracket_ratios(ratio, bracket)
+    out = []
+    for b in range(img_u8.shape[0]):
+        frames, h, w = render_ratios(net, img_u8[b], rs[b], bgr=bgr, batch=batch, ensemble=ensemble)
+        out.append(postprocess(fu.fuse(frames, h, w, fusion).unsqueeze(0), h, w, bgr=bgr))
+    return torch.cat(out)
+
+
+@torch.no_grad()
 def enhance_frame_tiled(net, lpnet, img_u8, tile, bgr=True, ratio_mode="lolblur", ratio_from="frame", ratio=None, gt_u8=None, overlap=0,
-                        batch=8, run=None, blend="average", ensemble=1):
+                        batch=8, run=None, blend="average", ensemble=1, bracket=None, fusion=(1, 1, 1)):
     """One uint8 frame [h,w,3] through the tiled route -> (uint8 [h,w,3], ratio [T,1]).  tile: (crop_h, crop_w) or "auto" (which must
     resolve to a tile here); ratio_mode / ratio_from / ratio / gt_u8 as tile_ratio takes them.  run(tiles, ratio) -> outs replaces
     tiling.run_tiles(net, tiles, ratio, batch) - the drivers pass the root's side of tiling.run_tiles_sharded.  blend: how the tiles are
     merged, "average" or "feather" (tiling.merge_u8); the merge runs here, on the root, whoever ran the tiles.  ensemble: copies of every
     tile through FDN with the tile's ratio, averaged before the merge (tiling.run_tiles); not with a caller's `run`, whose ranks are set
-    up for one tile shape."""
+    up for one tile shape.  bracket / fusion as in enhance_u8: the tiles' ratio is taken as without a bracket (ratio_from unchanged), every
+    stop scales it and runs the tiled route to a merged fp32 frame (a caller's `run` serves every stop), and the merged frames are fused;
+    the ratio returned is the one without the stops."""
     from . import tiling
     from .ensemble import check_ensemble
     tiling.check_blend(blend)
@@ -253,17 +330,24 @@ def enhance_frame_tiled(net, lpnet, img_u8, tile, bgr=True, ratio_mode="lolblur"
         raise FdnHipError(f"a {h}x{w} frame needs no tile: run it on the untiled path")
     tiles, ij = tiling.split_u8(img_u8, crop[0], crop[1], bgr=bgr, overlap=overlap)
     r = tile_ratio(lpnet, img_u8, tiles, ratio_mode, ratio_from, bgr=bgr, ratio=ratio, gt_u8=gt_u8, batch=batch)
+    if bracket is not None:
+        from . import fusion as fu
+        rs = fu.bracket_ratios(r, bracket).transpose(0, 1)                # [K,T,1]
+        frames = render_ratios(net, img_u8, rs, bgr=bgr, tile=crop, overlap=overlap, batch=batch, blend=blend, ensemble=ensemble, run=run,
+                               split=(tiles, ij))[0]
+        return postprocess(fu.fuse(frames, h, w, fu.check_exponents(fusion)).unsqueeze(0), h, w, bgr=bgr)[0], r
     outs = tiling.run_tiles(net, tiles, r, batch, ensemble=ensemble) if run is None else run(tiles, r)
     return tiling.merge_u8(outs, ij, h, w, bgr=bgr, blend=blend), r
 
 
 @torch.no_grad()
 def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=True, tile=None, ratio_from="frame", overlap=0, batch=8,
-                blend="average", ensemble=1, correct=None, sharpness=False):
+                blend="average", ensemble=1, correct=None, sharpness=False, bracket=None, fusion=(1, 1, 1), ratio=None):
     """One validation step of the reference (image_restoration_model.py:578-586, :650-658, :746-748, :844-848) for a batch, on the device:
     uint8 low-quality and ground-truth frames [B,h,w,3] -> (uint8 result [B,h,w,3], PSNR list, SSIM list, ratio [B,1]).
     ratio_mode: "gt" feeds mean(gray(lq)) / mean(gray(gt)) as the validation does (gt_ratio; lpnet is not used and may be None),
-    "lolblur" / "lolv1" feed LPNet's ratio as enhance_u8 does.  The scores are calculate_psnr / calculate_ssim of the uint8 result
+    "lolblur" / "lolv1" feed LPNet's ratio as enhance_u8 does, "fixed" the caller's `ratio` [B,1] (neither the ground truth's nor LPNet's:
+    what a chosen brightness scores).  The scores are calculate_psnr / calculate_ssim of the uint8 result
     (img1) against gt_u8, as the reference scores tensor2img's images (fdn_hip.metrics.calculate_psnr_ssim_u8).  Eager forward on the
     caller's stream.
     tile / ratio_from / overlap / batch / blend as in enhance_u8; ratio_from "tile" is the reference's val.grids validation.  With a tile
@@ -271,7 +355,9 @@ def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=Tr
     correct: None, or "gt_mean" / "mean_var": two more values are returned, the PSNR list and the SSIM list of the result after that
     brightness correction towards gt_u8 (fdn_hip.correct.calculate_psnr_ssim_corrected_u8); the first four are what they are without.
     sharpness: True appends one more value after those, the list of fdn_hip.sharpness.sharpness_metrics(gt_u8, result): per frame the
-    edge error, GMSD and the mean gradients with their ratio."""
+    edge error, GMSD and the mean gradients with their ratio.
+    bracket / fusion as in enhance_u8: the result scored is the fusion of the frame's renderings at the stops around the ratio fed
+    without a bracket, which is the ratio returned."""
     from .ensemble import check_ensemble
     from .metrics import calculate_psnr_ssim_u8
     from .tiling import check_blend
@@ -288,11 +374,14 @@ def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=Tr
             from .sharpness import sharpness_metrics
             res += (sharpness_metrics(gt_u8, out, bgr=bgr),)
         return res
-    if ratio_mode not in ("gt", "lolblur", "lolv1"):
-        raise ValueError(f"ratio_mode {ratio_mode!r}")
+    if ratio_mode not in ("gt", "lolblur", "lolv1", "fixed") or (ratio_mode == "fixed" and ratio is None):
+        raise ValueError(f"ratio_mode {ratio_mode!r}" + (" needs ratio [B,1]" if ratio_mode == "fixed" else ""))
     check_blend(blend)
     check_ensemble(ensemble)
-    if ratio_mode != "gt" and lpnet is None:
+    if bracket is not None:
+        from .fusion import check_bracket, check_exponents
+        bracket, fusion = check_bracket(bracket), check_exponents(fusion)
+    if ratio_mode not in ("gt", "fixed") and lpnet is None:
         raise FdnHipError(f"ratio_mode {ratio_mode!r} needs lpnet")
     if lq_u8.dim() == 3:
         lq_u8 = lq_u8.unsqueeze(0)
@@ -300,19 +389,27 @@ def validate_u8(net, lpnet, lq_u8, gt_u8, ratio_mode="gt", crop_border=0, bgr=Tr
         gt_u8 = gt_u8.unsqueeze(0)
     if lq_u8.shape != gt_u8.shape:
         raise FdnHipError(f"Image shapes are different: {tuple(lq_u8.shape)}, {tuple(gt_u8.shape)}.")
+    if ratio_mode == "fixed" and tuple(ratio.shape) != (lq_u8.shape[0], 1):
+        raise FdnHipError(f"ratio_mode 'fixed' needs ratio [B,1] for B = {lq_u8.shape[0]}")
     if tile is not None and lq_u8.dim() == 4 and resolve_tile(tile, lq_u8.shape[1], lq_u8.shape[2]) is not None:
         done = [enhance_frame_tiled(net, lpnet, lq_u8[b], tile, bgr=bgr, ratio_mode=ratio_mode, ratio_from=ratio_from, gt_u8=gt_u8[b],
-                                    overlap=overlap, batch=batch, blend=blend, ensemble=ensemble) for b in range(lq_u8.shape[0])]
+                                    ratio=None if ratio is None else ratio[b].reshape(-1, 1),
+                                    overlap=overlap, batch=batch, blend=blend, ensemble=ensemble, bracket=bracket, fusion=fusion)
+                for b in range(lq_u8.shape[0])]
         return scored(torch.stack([o for o, _ in done]), torch.stack([r for _, r in done]))
     x, h, w = preprocess(lq_u8, bgr=bgr)
     if ratio_mode == "gt":
         ratio = gt_ratio(x, preprocess(gt_u8, bgr=bgr)[0])
+    elif ratio_mode == "fixed":
+        ratio = ratio.to(device=x.device, dtype=torch.float32)
     elif ratio_mode == "lolblur":
         ratio = lpnet(x)
     else:
         ratio = lolv1_ratio(x, lpnet(x))
     ratio = ratio.contiguous()
-    if ensemble != 1:
+    if bracket is not None:
+        out = _bracket_u8(net, lq_u8, ratio, bracket, fusion, batch, ensemble, bgr)
+    elif ensemble != 1:
         out = _ensemble_u8(net, lq_u8, ratio, ensemble, batch, h, w, bgr)
     else:
         out = postprocess(net(x, ratio_i=ratio, device=x.device)[0].contiguous(), h, w, bgr=bgr)

@@ -18,6 +18,12 @@ with --tile, rank 0 reads, splits, merges and writes, and the tiles of each fram
 --ensemble 2|4|8 is the geometric self-ensemble (fdn_hip.ensemble): every frame - or every tile - runs through FDN in that many flipped /
 transposed copies with the ratio of the untransformed frame, and the results, mapped back, are averaged: 2, 4 or 8 forwards per frame.
 One GPU only.  No accuracy gain has been measured with it here (no trained checkpoint at hand).
+
+--ratio VALUE feeds FDN that ratio for every frame instead of LPNet's (--lpnet is then not needed).  --bracket EV[,EV...] (for example
+-1,0,1) renders every frame at the ratio it would be fed times 2^-EV for every stop (a positive stop is brighter) and fuses the renderings
+into one locally exposed frame (fdn_hip.fusion: exposure fusion, Mertens et al. 2007): one forward per stop and frame.  --fusion-weights
+C,S,E are the exponents of contrast, saturation and well-exposedness in the fusion's weights (default 1,1,1).  No gain in any quality
+figure has been measured with it here (no trained checkpoint at hand).
 """
 import argparse
 import glob
@@ -85,6 +91,55 @@ def add_ensemble_arg(ap):
                          "default 1 (off)")
 
 
+def bracket_arg(s):
+    """--bracket: 'EV[,EV...]' -> a tuple of 1 to 16 distinct finite exposure stops (fdn_hip.fusion.check_bracket)"""
+    from fdn_hip.fusion import check_bracket
+    try:
+        return check_bracket([float(v) for v in s.split(",")])
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"{s!r}: {e}")
+
+
+def fusion_weights_arg(s):
+    """--fusion-weights: 'C,S,E' -> three finite exponents >= 0 (fdn_hip.fusion.check_exponents)"""
+    from fdn_hip.fusion import check_exponents
+    try:
+        return check_exponents([float(v) for v in s.split(",")])
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"{s!r}: {e}")
+
+
+def ratio_value(s):
+    """--ratio VALUE: a finite float"""
+    try:
+        v = float(s)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{s!r} is not a number")
+    if v != v or v in (float("inf"), float("-inf")):
+        raise argparse.ArgumentTypeError(f"{s!r} is not finite")
+    return v
+
+
+def glue_bracket(argv):
+    """argv (None: the process's) with '--bracket' and the word after it joined by '=': argparse takes a value that begins with '-'
+    and is not a plain number, such as -1,0,1, for an option"""
+    argv = list(sys.argv[1:] if argv is None else argv)
+    out = []
+    while argv:
+        tok = argv.pop(0)
+        out.append(tok + "=" + argv.pop(0) if tok == "--bracket" and argv else tok)
+    return out
+
+
+def add_fusion_args(ap):
+    """--bracket / --fusion-weights: exposure fusion of every frame's renderings at a bracket of ratios (fdn_hip.fusion)"""
+    ap.add_argument("--bracket", type=bracket_arg, default=None, metavar="EV[,EV...]",
+                    help="render every frame at its ratio times 2^-EV for each of these 1 to 16 exposure stops (positive: brighter), for "
+                         "example -1,0,1, and fuse the renderings into one locally exposed frame; default off")
+    ap.add_argument("--fusion-weights", type=fusion_weights_arg, default=(1.0, 1.0, 1.0), metavar="C,S,E",
+                    help="with --bracket: the exponents of contrast, saturation and well-exposedness in the fusion's weights (default 1,1,1)")
+
+
 _hinted = False
 
 
@@ -124,12 +179,13 @@ def hint_hard_seam(tile, blend, overlap, h, w):
             return
 
 
-def run_driver(doc, build_models, ratio_mode="lolblur", fdn_keys="FDN checkpoint ({'params': state_dict}, 1503 keys)"):
-    """The directory walk shared by the LOL-Blur and LOL-v1 drivers: build_models() -> (FDN-like module, LPNet module) on the CPU,
-    ratio_mode as fdn_hip.harness.enhance_u8 takes it."""
+def parse_driver_args(doc, fdn_keys="FDN checkpoint ({'params': state_dict}, 1503 keys)", argv=None):
+    """the command line of the LOL-Blur and LOL-v1 drivers -> (parser, namespace)"""
     ap = argparse.ArgumentParser(description=doc, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--fdn", required=True, help=fdn_keys)
-    ap.add_argument("--lpnet", required=True, help="LPNet checkpoint (292 keys)")
+    ap.add_argument("--lpnet", default=None, help="LPNet checkpoint (292 keys); needed unless --ratio is given")
+    ap.add_argument("--ratio", type=ratio_value, default=None, metavar="VALUE",
+                    help="feed FDN this ratio for every frame instead of LPNet's (a smaller ratio is brighter)")
     ap.add_argument("--input", required=True, help="glob of input frames")
     ap.add_argument("--output", required=True, help="output directory")
     ap.add_argument("--input-root", default=None,
@@ -140,7 +196,17 @@ def run_driver(doc, build_models, ratio_mode="lolblur", fdn_keys="FDN checkpoint
     ap.add_argument("--device", default="cuda:0")
     add_tile_args(ap)
     add_ensemble_arg(ap)
-    a = ap.parse_args()
+    add_fusion_args(ap)
+    a = ap.parse_args(glue_bracket(argv))
+    if a.ratio is None and not a.lpnet:
+        ap.error("--lpnet is needed unless --ratio VALUE is given")
+    return ap, a
+
+
+def run_driver(doc, build_models, ratio_mode="lolblur", fdn_keys="FDN checkpoint ({'params': state_dict}, 1503 keys)"):
+    """The directory walk shared by the LOL-Blur and LOL-v1 drivers: build_models() -> (FDN-like module, LPNet module) on the CPU,
+    ratio_mode as fdn_hip.harness.enhance_u8 takes it."""
+    ap, a = parse_driver_args(doc, fdn_keys)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1 and a.ensemble > 1:
         ap.error("--ensemble above 1 runs on one GPU only: the sharded tile server takes one tile shape")
@@ -161,10 +227,19 @@ def run_driver(doc, build_models, ratio_mode="lolblur", fdn_keys="FDN checkpoint
     net, lp = build_models()
     net = net.to(dev).eval()
     net.load_state_dict(load_params(a.fdn), strict=True)
-    lp = lp.to(dev).eval()
-    lp.load_state_dict(load_params(a.lpnet), strict=True)
+    if a.ratio is None:
+        lp = lp.to(dev).eval()
+        lp.load_state_dict(load_params(a.lpnet), strict=True)
+    else:
+        lp, ratio_mode = None, "fixed"
 
     tile_kw = dict(ratio_from=a.tile_ratio, overlap=a.tile_overlap, batch=a.batch, blend=a.tile_blend)
+    if a.bracket is not None:                                            # without the option every call is what it was
+        tile_kw.update(bracket=a.bracket, fusion=a.fusion_weights)
+
+    def fixed(n):
+        """the ratio keyword of a call on n frames: --ratio for each of them, or nothing"""
+        return {} if a.ratio is None else {"ratio": torch.full((n, 1), a.ratio, dtype=torch.float32, device=dev)}
 
     def serve(tiles, ratio):
         return tiling.run_tiles(net, tiles, ratio, a.batch)
@@ -180,10 +255,12 @@ def run_driver(doc, build_models, ratio_mode="lolblur", fdn_keys="FDN checkpoint
         hint_large_frame(a.tile, h, w)
         hint_hard_seam(a.tile, a.tile_blend, a.tile_overlap, h, w)
         if dist is None:
-            return enhance_u8(net, lp, batch, bgr=False, ratio_mode=ratio_mode, tile=a.tile, ensemble=a.ensemble, **tile_kw)
+            return enhance_u8(net, lp, batch, bgr=False, ratio_mode=ratio_mode, tile=a.tile, ensemble=a.ensemble, **fixed(len(batch)),
+                              **tile_kw)
         if resolve_tile(a.tile, h, w) is None:
-            return enhance_u8(net, lp, batch, bgr=False, ratio_mode=ratio_mode)
-        return torch.stack([enhance_frame_tiled(net, lp, img, a.tile, bgr=False, ratio_mode=ratio_mode,
+            return enhance_u8(net, lp, batch, bgr=False, ratio_mode=ratio_mode, **fixed(len(batch)),
+                              **({k: v for k, v in tile_kw.items() if k in ("bracket", "fusion")}))
+        return torch.stack([enhance_frame_tiled(net, lp, img, a.tile, bgr=False, ratio_mode=ratio_mode, **fixed(1),
                                                 run=lambda t, r: tiling.run_tiles_root(dist, serve, t, r), **tile_kw)[0] for img in batch])
 
     try:

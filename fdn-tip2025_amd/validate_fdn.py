@@ -5,7 +5,9 @@ calculate_psnr / calculate_ssim on the 8-bit images), without the training frame
     decode (PIL, worker threads) -> uint8 on the GPU -> fdn_pre_u8 -> ratio -> FDN -> fdn_post_u8 -> PSNR / SSIM against the ground truth
 
 --ratio gt feeds FDN mean(gray(lq)) / mean(gray(gt)) as the validation does (:650-654; no LPNet needed), --ratio lpnet the ratio the
-inference drivers feed (LPNet's prediction for --variant lolblur, mean(gray) / prediction for lolv1).  --lq and --gt are globs, sorted
+inference drivers feed (LPNet's prediction for --variant lolblur, mean(gray) / prediction for lolv1), --ratio VALUE that number for every
+frame.  --bracket EV[,EV...] scores the exposure fusion (fdn_hip.fusion) of every frame's renderings at that ratio times 2^-EV per stop,
+weighted with the exponents --fusion-weights C,S,E (inference_fdn_lolblur.py has what they mean; not what the reference scores).  --lq and --gt are globs, sorted
 and paired by index; frames of equal size are batched and decoded one batch ahead.  The frames leave the GPU only with --output; the
 scores take one small copy per batch.  Needs a ROCm GPU and the built libfdn_hip.so; there is no CPU fallback.
 
@@ -60,6 +62,17 @@ def output_paths(lq_paths, output):
     return dest
 
 
+def ratio_arg(s):
+    """--ratio: gt, lpnet, or a number"""
+    if s in ("gt", "lpnet"):
+        return s
+    from inference_fdn_lolblur import ratio_value
+    try:
+        return ratio_value(s)
+    except argparse.ArgumentTypeError:
+        raise argparse.ArgumentTypeError(f"{s!r}: gt, lpnet or a finite number")
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--fdn", required=True, help="FDN checkpoint ({'params': state_dict})")
@@ -67,15 +80,21 @@ def parse_args(argv=None):
     ap.add_argument("--lq", required=True, help="low-quality input frames: a glob, sorted")
     ap.add_argument("--gt", required=True, help="ground-truth frames: a glob, sorted and paired with --lq by index")
     ap.add_argument("--variant", choices=("lolblur", "lolv1"), default="lolblur", help="FDN (dim 32) or FDN_lolv1 (dim 24)")
-    ap.add_argument("--ratio", choices=("gt", "lpnet"), default="gt", help="where ratio_i comes from: the ground truth (validation) or LPNet")
+    ap.add_argument("--ratio", type=ratio_arg, default="gt", metavar="gt|lpnet|VALUE",
+                    help="where ratio_i comes from: the ground truth (validation), LPNet, or this number for every frame")
     ap.add_argument("--crop_border", type=int, default=0, help="pixels cut from every edge before scoring")
     ap.add_argument("--output", default=None, help="directory for the restored frames; without it no frame is written")
     ap.add_argument("--csv", default=None, help="file for one 'frame,psnr,ssim,ratio' line per pair")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--device", default="cuda:0")
-    from inference_fdn_lolblur import add_ensemble_arg, add_tile_args
+    from inference_fdn_lolblur import add_ensemble_arg, add_tile_args, bracket_arg, fusion_weights_arg, glue_bracket
     add_tile_args(ap, ratio_default="tile")
     add_ensemble_arg(ap)
+    # absent unless given, as the flags below
+    ap.add_argument("--bracket", type=bracket_arg, default=argparse.SUPPRESS, metavar="EV[,EV...]",
+                    help="score the exposure fusion of every frame's renderings at its ratio times 2^-EV for each of these stops")
+    ap.add_argument("--fusion-weights", type=fusion_weights_arg, default=argparse.SUPPRESS, metavar="C,S,E",
+                    help="with --bracket: the exponents of contrast, saturation and well-exposedness (default 1,1,1)")
     ap.add_argument("--fourier", action="store_true", help="also split every frame's error into amplitude and phase per frequency band")
     ap.add_argument("--fourier-bands", type=int, default=8, help="radial frequency bands besides the zero-frequency bin (1 .. 32)")
     # absent unless given, so that the namespace of a command line without them is what it was
@@ -86,13 +105,15 @@ def parse_args(argv=None):
                     help="also score every frame after a brightness correction towards the ground truth (fdn_hip.correct)")
     ap.add_argument("--sharpness", action="store_true", default=argparse.SUPPRESS,
                     help="also score the edge error, GMSD and the mean-gradient ratio against the ground truth (fdn_hip.sharpness)")
-    a = ap.parse_args(argv)
+    a = ap.parse_args(glue_bracket(argv))
     if not 1 <= a.fourier_bands <= 32:
         ap.error("--fourier-bands must be in 1 .. 32")
     if hasattr(a, "loe_size") and not hasattr(a, "lowlight"):
         ap.error("--loe-size needs --lowlight")
     if getattr(a, "loe_size", 0) < 0:
         ap.error("--loe-size must be >= 0")
+    if hasattr(a, "fusion_weights") and not hasattr(a, "bracket"):
+        ap.error("--fusion-weights needs --bracket")
     if a.ratio == "lpnet" and not a.lpnet:
         ap.error("--ratio lpnet needs --lpnet")
     if a.crop_border < 0:
@@ -149,7 +170,11 @@ def main(argv=None):
     if a.ratio == "lpnet":
         lp = I_predict_net().to(dev).eval()
         lp.load_state_dict(load_params(a.lpnet), strict=True)
-    mode = RATIO_MODE[(a.ratio, a.variant)]
+    fixed = not isinstance(a.ratio, str)
+    mode = "fixed" if fixed else RATIO_MODE[(a.ratio, a.variant)]
+    more = {"correct": mode_corr} if mode_corr else {}
+    if hasattr(a, "bracket"):
+        more.update(bracket=a.bracket, fusion=getattr(a, "fusion_weights", (1.0, 1.0, 1.0)))
 
     n = len(a.pairs)
     psnr, ssim, ratio, fourier, ll, corr, sh = [None] * n, [None] * n, [None] * n, [None] * n, [None] * n, [None] * n, [None] * n
@@ -161,7 +186,8 @@ def main(argv=None):
             hint_hard_seam(a.tile, a.tile_blend, a.tile_overlap, lqs.shape[1], lqs.shape[2])
             out, p, s, r, *pc = validate_u8(net, lp, lq, gt, ratio_mode=mode, crop_border=a.crop_border, bgr=False, tile=a.tile,
                                             ratio_from=a.tile_ratio, overlap=a.tile_overlap, batch=a.batch, blend=a.tile_blend,
-                                            ensemble=a.ensemble, **({"correct": mode_corr} if mode_corr else {}))
+                                            ensemble=a.ensemble, **more,
+                                            **({"ratio": torch.full((lq.shape[0], 1), a.ratio, dtype=torch.float32, device=dev)} if fixed else {}))
             r = r.reshape(r.shape[0], -1).cpu().tolist()              # one ratio per frame, or one per tile of a tiled frame
             frames = out.cpu().numpy() if a.dest else None
             if a.fourier:
