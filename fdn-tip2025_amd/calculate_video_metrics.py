@@ -6,11 +6,18 @@ own reader, and no detour through 8-bit RGB, so 10 bit is scored as 10 bit.  No 
     python calculate_video_metrics.py --ref gt.y4m enhanced.y4m --csv scores.csv
     ffmpeg -i out.mp4 -f yuv4mpegpipe -strict -1 - | python calculate_video_metrics.py --ref gt.y4m -
     python calculate_video_metrics.py --size 1280x720 --pix-fmt nv12 enhanced.yuv          # no ground truth: mean luma, cuts, flicker
+    python calculate_video_metrics.py --ref gt.y4m enhanced.y4m --motion --motion-radius 12   # and the motion-compensated figures
 
 REF and DIST are paths, DIST may be `-` for stdin.  PSNR is on the codes (peak 2^bits - 1) whatever the range of the stream, the `average`
 pools the three planes as ffmpeg's psnr filter does; SSIM is the reference's _ssim_cly on the luma codes; mean_y and dmean (the change of
 mean luma against the frame before, `-` at a scene cut) are in 8-bit code units; flicker = mean |dmean| over the frames that are no cut.
 With --ref the cuts are found in REF.  stdout: one line per frame, `Average:` and `flicker:`; every message goes to stderr.  Streams of
+--motion adds the motion-compensated temporal consistency (fdn_hip.motion.MotionScore, libfdn_motion.so): block vectors found in REF (in
+DIST itself without one, which flatters it) by full search over +-N pixels (--motion-radius, default 8), and along them mc-PSNR (how well
+the previous output frame predicts this one; `ref`: the same on REF, the ceiling), tc (the RMS difference of DIST's compensated change
+against REF's, 8-bit code units: the local counterpart of the flicker figure) and the share of moving blocks; `-` at a scene cut.  Each
+frame line, the CSV (mc_psnr, mc_psnr_ref, tc_rmse, moving, mean_mv) and one line `temporal:` after `flicker:` carry them; without
+--motion stdout and the CSV are what they were.  Streams of
 unequal length: the common prefix is scored, both lengths are named and the exit status is 1.  One process, one GPU; needs a ROCm GPU
 and the built libfdn_hip.so, there is no CPU fallback.
 """
@@ -24,6 +31,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from inference_fdn_video import SAMPLE_BYTES, open_video, say, size_arg, unit_fraction  # noqa: E402
 
 ME = "calculate_video_metrics.py"
+MOTION_COLUMNS = ("mc_psnr", "mc_psnr_ref", "tc_rmse", "moving", "mean_mv")     # after CSV_COLUMNS, with --motion
 CSV_COLUMNS = ("frame", "psnr_y", "psnr_u", "psnr_v", "psnr_avg", "ssim_y", "mean_y_ref", "mean_y", "cut", "dmean_ref", "dmean")
 
 
@@ -39,11 +47,20 @@ def parse_args(argv=None):
     ap.add_argument("--scene-cut", type=unit_fraction(False), default=0.3, metavar="FRACTION",
                     help="a scene cut is where more than this fraction of the pixels changed their luma bin (of 256) against the frame "
                          "before; 1 = never (default 0.3)")
+    ap.add_argument("--motion", action="store_true",
+                    help="add the motion-compensated temporal consistency: mc-PSNR, tc, moving blocks (vectors from REF, else from DIST)")
+    ap.add_argument("--motion-radius", type=int, default=None, metavar="N", help="search +-N pixels around every 16 x 16 block, 0 .. 16 (default 8)")
     ap.add_argument("--csv", default=None, metavar="PATH", help="write the per-frame records there, floats as repr() writes them")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
     if a.batch < 1:
         ap.error("--batch must be at least 1")
+    if a.motion_radius is not None and not a.motion:
+        ap.error("--motion-radius needs --motion")
+    if a.motion_radius is None:
+        a.motion_radius = 8
+    if not 0 <= a.motion_radius <= 16:
+        ap.error("--motion-radius must be in 0 .. 16")
     if a.ref == "-":
         ap.error("REF is a path: only DIST may be stdin")
     return a
@@ -103,6 +120,17 @@ def frame_line(i, r, has_ref):
     return f"{i:6d}: mean_y {r['mean_y']:.3f}, cut {int(r['cut'])}, dmean {_num(r['dmean'], '+.4f')}"
 
 
+def motion_part(m, has_ref):
+    """what --motion adds to a frame line"""
+    ref = f" (ref {_num(m['mc_psnr_ref'], '.4f')})" if has_ref else ""
+    tc = f", tc {_num(m['tc_rmse'], '.4f')}" if has_ref else ""
+    return f", mc-PSNR {_num(m['mc_psnr'], '.4f')}{ref}{tc}, moving {_num(m['moving'], '.3f')}"
+
+
+def motion_cells(m):
+    return ",".join("" if m[k] is None else repr(float(m[k])) for k in MOTION_COLUMNS)
+
+
 def csv_row(i, r):
     def cell(k):
         v = i if k == "frame" else r[k]
@@ -135,13 +163,17 @@ def score_streams(a, dist, ref, fmt, w, h):
     dev = torch.device(a.device)
     torch.cuda.set_device(dev)
     score = VideoScore(h, w, fmt, cut=a.scene_cut, device=dev)
+    motion = None
+    if a.motion:
+        from fdn_hip.motion import MotionScore
+        motion = MotionScore(h, w, fmt, radius=a.motion_radius, device=dev)
     n = fmt.frame_samples(h, w)
     as_bytes = lambda t: t.numpy().view(np.uint8).reshape(a.batch, -1)  # noqa: E731
     buf_d = torch.empty((a.batch, n), dtype=fmt.dtype)
     buf_r = torch.empty((a.batch, n), dtype=fmt.dtype) if ref is not None else None
     out = open(a.csv, "w") if a.csv else None
     if out:
-        out.write(",".join(CSV_COLUMNS) + "\n")
+        out.write(",".join(CSV_COLUMNS + (MOTION_COLUMNS if motion else ())) + "\n")
     done = 0
     try:
         while True:
@@ -149,11 +181,13 @@ def score_streams(a, dist, ref, fmt, w, h):
             nr = ref.read_batch(as_bytes(buf_r)) if ref is not None else nd
             k = min(nd, nr)
             if k:
-                recs = score.update(buf_d[:k].to(dev), None if ref is None else buf_r[:k].to(dev))
-                for r in recs:
-                    print(frame_line(done, r, ref is not None))
+                on_d, on_r = buf_d[:k].to(dev), (None if ref is None else buf_r[:k].to(dev))
+                recs = score.update(on_d, on_r)
+                mrecs = motion.update(on_d, on_r, cuts=[r["cut"] for r in recs]) if motion else [None] * k
+                for r, m in zip(recs, mrecs):
+                    print(frame_line(done, r, ref is not None) + (motion_part(m, ref is not None) if motion else ""))
                     if out:
-                        out.write(csv_row(done, r) + "\n")
+                        out.write(csv_row(done, r) + ("," + motion_cells(m) if motion else "") + "\n")
                     done += 1
             if nd < a.batch or nr < a.batch:
                 break
@@ -173,6 +207,12 @@ def score_streams(a, dist, ref, fmt, w, h):
         if s["flicker"] == s["flicker"]:                                  # not nan: some frame followed a frame of its scene
             print(f"flicker: {s['flicker']:.4f}" + (f" (ref {s['flicker_ref']:.4f}, against ref {s['flicker_err']:.4f})" if ref is not None else "")
                   + " mean |dmean|, 8-bit code units")
+        t = motion.summary() if motion else None
+        if t and t["mc_psnr"] == t["mc_psnr"]:                            # not nan: some frame followed a frame of its scene
+            print(f"temporal: mc-PSNR {t['mc_psnr']:.4f} dB (over the stream {t['mc_psnr_global']:.4f})"
+                  + (f", ref {t['mc_psnr_ref']:.4f} dB (over the stream {t['mc_psnr_ref_global']:.4f}), tc {t['tc_rmse']:.4f} (over the stream "
+                     f"{t['tc_rmse_global']:.4f}) RMS against ref, 8-bit code units" if ref is not None else "")
+                  + f", moving {t['moving']:.3f}, mean |mv| {t['mean_mv']:.3f}, search +-{a.motion_radius}")
     sys.stdout.flush()
     for rd, path in ((dist, a.dist), (ref, a.ref)):
         if rd is not None and rd.error:                                   # a stream cut mid-frame, as the video driver words it
