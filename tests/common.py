@@ -1,14 +1,74 @@
 """Shared helpers for the parity tests (fixtures, synthetic weights, tolerance policy)."""
+import contextlib
 import json
 import os
 
 import numpy as np
 import torch
+import torch.utils.deterministic
 
 from weights import synth_state_dict
 
+try:
+    import pytest
+except ImportError:         # bench.py, smoke() and the tools import this module for the weights: they need no fixture
+    pytest = None
+
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SEED = 7  # tests/golden/make_golden.py
+
+
+# ---- poisoned uninitialised memory (testing) ----
+# The wrappers allocate outputs and workspace with torch.empty, and torch's caching allocator hands a freed block to the next request of its
+# size: the second of two equal calls would find the first one's answer in its output.  Under poisoned() every torch.empty / empty_like /
+# new_empty / empty_strided is filled with NaN (floating types) or the type's maximum (integers), so each assertion of a GPU module also says
+# "every element was written and no unwritten element was read".
+def _poison_state():
+    return (torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled(),
+            torch.utils.deterministic.fill_uninitialized_memory)
+
+
+@contextlib.contextmanager
+def _poison_set(mode, warn_only, fill):
+    prev = _poison_state()
+    torch.use_deterministic_algorithms(mode, warn_only=warn_only)
+    torch.utils.deterministic.fill_uninitialized_memory = fill
+    try:
+        yield
+    finally:
+        torch.use_deterministic_algorithms(prev[0], warn_only=prev[1])
+        torch.utils.deterministic.fill_uninitialized_memory = prev[2]
+
+
+def poisoned():
+    """Context manager: torch fills uninitialised allocations (deterministic mode, warn_only so that an op without a deterministic form warns
+    and runs).  Restores mode, warn_only and the fill flag on exit, also on an exception; nests."""
+    return _poison_set(True, True, True)
+
+
+def poisoned_off():
+    """Context manager for a test listed in POISON_EXEMPT: torch's defaults (no deterministic mode, no fill) inside, the previous state after."""
+    return _poison_set(False, False, False)
+
+
+def poison_uninitialized():
+    """Every tests/test_gpu_*.py imports this: module-scoped, so that module-scoped fixtures (models, weight files) are built under it too."""
+    with poisoned():
+        yield
+
+
+if pytest is not None:
+    poison_uninitialized = pytest.fixture(scope="module", autouse=True)(poison_uninitialized)
+
+
+# test id ("<module>::<test function>") -> reason.  The only way out of the fixture: a `with poisoned_off():` inside that test.  The only
+# admissible reason is that torch's deterministic mode changes or refuses a torch op the test or a wrapper uses, with the op named; a NaN
+# that comes out of a library call is never one.  tests/test_poison_cpu.py holds the list to the modules.
+POISON_EXEMPT = {
+    # not a torch-mode side effect but the switch's own test: it has to see an allocation made while the fill is off
+    "test_gpu_poison::test_the_block_a_freed_result_leaves_is_what_the_next_call_gets":
+        "tests the switch itself: torch.empty outside poisoned() must hand back the freed block unfilled, and be forced again after",
+}
 
 
 def fixture(name):

@@ -23,6 +23,7 @@ import correct_ref as ref
 import fdn_oracle as O
 from common import fdn_weights
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "fdn-tip2025_amd")

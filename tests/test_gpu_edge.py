@@ -13,6 +13,7 @@ import edge_cases as EC
 import fdn_oracle as O
 from common import assert_close_cond, fdn_weights, fixture, fixture_weights, lpnet_weights, rel_rms
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 

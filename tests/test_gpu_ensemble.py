@@ -24,6 +24,7 @@ import d4_ref as ref
 import fdn_oracle as O
 from common import fdn_weights, lpnet_weights
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(33, 65), (70, 90), (32, 32), (34, 300), (5, 7)]

@@ -8,6 +8,7 @@ import torch
 import fdn_oracle as O
 from common import assert_close_cond, fixture, fixture_weights, rel_rms
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 
 

@@ -6,6 +6,7 @@ float64 is then the pair's (tests/test_gpu_parity.py::test_fdsa runs the module,
 import pytest
 import torch
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 
 

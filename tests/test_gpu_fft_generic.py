@@ -14,6 +14,7 @@ import torch
 
 from common import FFT_COL_ROUTES, FFT_ROW_ROUTES, fcaffn_ref, rel_rms
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 
 COLS = sorted(H for H, r in FFT_COL_ROUTES.items() if r[0] != "refused")

@@ -9,6 +9,7 @@ import torch
 
 from common import PLANNED_H, PLANNED_W, fcaffn_ref as _fcaffn_ref, rel_rms
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 
 

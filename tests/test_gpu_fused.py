@@ -9,6 +9,7 @@ import torch
 import fdn_oracle as O
 from common import fdn_weights, fixture, fixture_weights, lpnet_weights, rel_rms
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 
 

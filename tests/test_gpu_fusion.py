@@ -22,6 +22,7 @@ import fusion_ref as ref
 from common import fdn_weights
 from test_fusion_cpu import check_argument_errors
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "fdn-tip2025_amd")

@@ -54,6 +54,7 @@ import torch
 import fdn_oracle as O
 from common import CONV1X1_GEOMETRY_ROUTES, assert_close_cond, conv1x1_route_name, rel_rms
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 F = torch.nn.functional
 D = torch.float64

@@ -15,6 +15,7 @@ import fdn_oracle as O
 from common import assert_close_cond, rel_rms
 from test_gpu_geometry import _core, _mid
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 F = torch.nn.functional
 D = torch.float64

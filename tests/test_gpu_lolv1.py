@@ -9,6 +9,7 @@ import torch
 import fdn_oracle as O
 from common import assert_close_cond, fixture, fixture_weights, lolv1_weights, lpnet_weights
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 F64 = torch.float64
 

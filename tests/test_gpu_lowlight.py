@@ -17,6 +17,7 @@ import __graft_entry__ as entry  # noqa: F401  (puts the package on sys.path)
 import lowlight_ref as ref
 from common import fdn_weights
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "fdn-tip2025_amd")
 

@@ -17,6 +17,7 @@ import fdn_oracle as O
 from common import fdn_weights, lpnet_weights
 from test_paired_cpu import chw, paired_cases
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "fdn-tip2025_amd")

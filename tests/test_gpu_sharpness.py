@@ -33,6 +33,7 @@ import sharpness_ref as ref
 from common import fdn_weights
 from test_sharpness_cpu import check_argument_errors
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "fdn-tip2025_amd")

@@ -20,6 +20,7 @@ import torch.nn.functional as F
 import fdn_oracle as O
 from common import assert_close_cond, lpnet_weights, rel_rms
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -24                # unit roundoff of fp32
 SENTINEL = -7777.0            # fills the memory a kernel must not write

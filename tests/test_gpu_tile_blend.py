@@ -33,6 +33,7 @@ if __name__ == "__main__":                                     # the child proce
 from common import fdn_weights, lpnet_weights  # noqa: E402
 from tile_blend_ref import merge64  # noqa: E402
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 
 SHAPES = [((70, 90), 0), ((70, 90), 8), ((70, 90), 20), ((40, 50), 0), ((64, 96), 0), ((32, 32), 0)]

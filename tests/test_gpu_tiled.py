@@ -30,6 +30,7 @@ if __name__ == "__main__":                                     # the child proce
 import fdn_oracle as O  # noqa: E402
 from common import fdn_weights, lpnet_weights  # noqa: E402
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 
 SHAPES = [((70, 90), (64, 64), 8), ((33, 65), (32, 32), 8), ((100, 200), (64, 96), 4), ((96, 128), (64, 64), 8), ((96, 160), (96, 160), 8)]

@@ -33,6 +33,7 @@ PKG = os.path.join(ROOT, "fdn-tip2025_amd")
 FMTS = list(ref.PIX_FMTS)
 KINDS = ("random", "near", "identical", "extreme")
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 
 

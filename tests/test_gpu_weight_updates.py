@@ -25,6 +25,7 @@ import lpips_ref as R
 from common import fdn_shapes, fdn_weights, fixture, fixture_weights, lolv1_shapes, lolv1_weights, lpnet_weights
 from weights import shapes_of, synth_state_dict
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 

@@ -31,6 +31,7 @@ from common import fdn_weights, lpnet_weights
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "fdn-tip2025_amd")
 
+from common import poison_uninitialized  # noqa: F401  (autouse, tests/common.py: torch.empty is filled with NaN / the integer maximum)
 pytestmark = pytest.mark.gpu
 
 IDS = [f"{h}x{w}" for h, w, _, _, _ in ref.SHAPES]
