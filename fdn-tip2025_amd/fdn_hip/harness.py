@@ -517,14 +517,16 @@ def postprocess_yuv420(result, h, w, fmt):
 
 @torch.no_grad()
 def enhance_yuv420(net, lpnet, frames, h, w, fmt, ratio_mode="lolblur", ratio=None, tile=None, ratio_from="frame", overlap=0, batch=8,
-                   blend="average", temporal=None):
+                   blend="average", temporal=None, denoise=None):
     """4:2:0 frames in -> 4:2:0 frames out, shaped and typed like the input, through LPNet -> FDN: enhance_u8 for video.  frames and fmt
     as preprocess_yuv420 takes them; every other keyword means what it means in enhance_u8.  Untiled, the batch goes through one forward;
     with a tile that resolve_tile turns into a crop, frame by frame: preprocess_yuv420(pad=False) -> tiling.split -> the ratio (from the
     reflect-padded frame, or per tile) -> tiling.run_tiles -> tiling.merge(blend) -> postprocess_yuv420.
     temporal: None, or the fdn_hip.temporal.RatioFilter of the stream these frames continue: what FDN would be fed per frame (frame_ratio:
     LPNet's prediction, or mean(gray) / LPNet for "lolv1") is filtered across the frames on the device, then fed as the "fixed" mode
-    feeds a ratio; with a tile the frame's filtered ratio goes to every tile (ratio_from "frame" only)."""
+    feeds a ratio; with a tile the frame's filtered ratio goes to every tile (ratio_from "frame" only).
+    denoise: None, or the fdn_hip.mctf.TemporalDenoiser of the stream these frames continue: the fp32 frame - the forward's result, or the
+    merged frame of the tiled route - goes through denoise.step before postprocess_yuv420 rounds it to samples."""
     from . import tiling
     if ratio_mode not in ("lolblur", "lolv1", "fixed"):
         raise ValueError(f"ratio_mode {ratio_mode!r}")
@@ -538,6 +540,8 @@ def enhance_yuv420(net, lpnet, frames, h, w, fmt, ratio_mode="lolblur", ratio=No
             raise ValueError(f"temporal filter is for {temporal.h}x{temporal.w} {temporal.bits}-bit frames, these are {h}x{w} {fmt.bits}-bit")
         if lpnet is None:
             raise FdnHipError(f"ratio_mode {ratio_mode!r} needs lpnet")
+    if denoise is not None and not denoise.matches(h, w, fmt.bits):
+        raise ValueError(f"temporal denoiser is for {denoise.h}x{denoise.w} {denoise.bits}-bit frames, these are {h}x{w} {fmt.bits}-bit")
     frames = _yuv_frames(frames, h, w, fmt)
     B = frames.shape[0]
     crop = resolve_tile(tile, h, w)
@@ -545,7 +549,10 @@ def enhance_yuv420(net, lpnet, frames, h, w, fmt, ratio_mode="lolblur", ratio=No
         x = preprocess_yuv420(frames, h, w, fmt)[0]
         if temporal is not None:
             ratio_mode, ratio = "fixed", temporal.step(frames, frame_ratio(lpnet, x, ratio_mode).contiguous())
-        return postprocess_yuv420(_forward(net, lpnet, x, ratio_mode, ratio).contiguous(), h, w, fmt).view(frames.dtype)
+        res = _forward(net, lpnet, x, ratio_mode, ratio).contiguous()
+        if denoise is not None:
+            res = denoise.step(res)
+        return postprocess_yuv420(res, h, w, fmt).view(frames.dtype)
     if ratio_mode == "fixed" and (ratio is None or ratio.shape[0] != B):
         raise FdnHipError(f"ratio_mode 'fixed' needs ratio [B,1] or [B,T,1] for B = {B}")
     ch, cw = tiling.effective_crop(h, w, *crop)
@@ -559,5 +566,8 @@ def enhance_yuv420(net, lpnet, frames, h, w, fmt, ratio_mode="lolblur", ratio=No
         else:
             r = _tile_ratio(lpnet, tiles, ratio_mode, ratio_from, None if ratio is None else ratio[b].reshape(-1, 1), batch,
                             lambda: preprocess_yuv420(frame, h, w, fmt)[0])
-        out.append(postprocess_yuv420(tiling.merge(tiling.run_tiles(net, tiles, r, batch), ij, h, w, blend), h, w, fmt))
+        res = tiling.merge(tiling.run_tiles(net, tiles, r, batch), ij, h, w, blend)
+        if denoise is not None:
+            res = denoise.step(res.contiguous())
+        out.append(postprocess_yuv420(res, h, w, fmt))
     return torch.cat(out).view(frames.dtype)

@@ -11,7 +11,9 @@ so a frame goes from the decoder's samples straight to fp32 and back, rounded on
 IN / OUT: paths, `-` = stdin / stdout (binary); every message goes to stderr.  The output has the input's container and format: for Y4M
 the input's header line is written back verbatim and `FRAME` precedes each frame.  Frames larger than one forward can take run with
 --tile, as in the image drivers.  --ratio-smooth ALPHA filters the ratio FDN is fed across the frames (fdn_hip.temporal: against the flicker
-of a ratio predicted frame by frame), --scene-cut FRACTION sets where it starts afresh.  One process, one GPU.  Needs a ROCm GPU and the built libfdn_hip.so; there is no CPU fallback.
+of a ratio predicted frame by frame), --scene-cut FRACTION sets where it starts afresh.  --temporal-denoise STRENGTH filters the enhanced
+frames themselves along block motion vectors, before they are rounded to samples (fdn_hip.mctf: against boiling noise; --denoise-threshold,
+--denoise-radius and --denoise-cut shape it).  One process, one GPU.  Needs a ROCm GPU and the built libfdn_hip.so; there is no CPU fallback.
 """
 import argparse
 import os
@@ -303,6 +305,29 @@ def unit_fraction(low_open):
     return parse
 
 
+def positive_float(s):
+    try:
+        v = float(s)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{s!r} is not a number")
+    if not 0.0 < v < float("inf"):
+        raise argparse.ArgumentTypeError(f"{s!r} is not a positive, finite number")
+    return v
+
+
+def radius_arg(s):
+    try:
+        v = int(s)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{s!r} is not an integer")
+    if not 0 <= v <= 16:
+        raise argparse.ArgumentTypeError(f"{s!r} is not in 0 .. 16")
+    return v
+
+
+DENOISE_DEFAULTS = {"denoise_threshold": 0.12, "denoise_radius": 8, "denoise_cut": 0.10}     # fdn_hip.mctf.TemporalDenoiser's own
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--fdn", required=True, help="FDN checkpoint ({'params': state_dict})")
@@ -326,12 +351,29 @@ def parse_args(argv=None):
     ap.add_argument("--scene-cut", type=unit_fraction(False), default=0.3, metavar="FRACTION",
                     help="with --ratio-smooth: a scene cut is where more than this fraction of the pixels changed their luma bin (of 256) "
                          "against the frame before; 1 = never (default 0.3)")
+    ap.add_argument("--temporal-denoise", type=unit_fraction(True), default=None, metavar="STRENGTH",
+                    help="filter the enhanced frames along block motion vectors against boiling noise: out = frame + k * (the previous "
+                         "output, motion-compensated - frame), k = STRENGTH in (0, 1] where the prediction fits, falling to 0 where it does "
+                         "not and at a scene cut (default: off)")
+    ap.add_argument("--denoise-threshold", type=positive_float, default=None, metavar="T",
+                    help="with --temporal-denoise: the local difference between a frame and its prediction, in units of the [0, 1] signal, at "
+                         "which k reaches 0 (default 0.12, from synthetic noise, not tuned on footage)")
+    ap.add_argument("--denoise-radius", type=radius_arg, default=None, metavar="R",
+                    help="with --temporal-denoise: the block search looks R pixels each way, 0 .. 16 (default 8)")
+    ap.add_argument("--denoise-cut", type=unit_fraction(False), default=None, metavar="FRACTION",
+                    help="with --temporal-denoise: a frame whose best block matches miss by more than this fraction of the luma range on "
+                         "average starts afresh, unfiltered; 1 = never (default 0.10)")
     add_tile_args(ap)
     a = ap.parse_args(argv)
     if a.batch < 1:
         ap.error("--batch must be at least 1")
     if a.ratio_smooth is not None and a.tile_ratio != "frame":
         ap.error("--ratio-smooth filters one ratio per frame: it needs --tile-ratio frame")
+    for k, v in DENOISE_DEFAULTS.items():
+        if getattr(a, k) is None:
+            setattr(a, k, v)
+        elif a.temporal_denoise is None:
+            ap.error(f"--{k.replace('_', '-')} needs --temporal-denoise")
     return a
 
 
@@ -364,9 +406,14 @@ def main():
         from fdn_hip.temporal import RatioFilter
         smooth = RatioFilter(h, w, fmt.bits, a.ratio_smooth, cut=a.scene_cut, device=dev)
 
+    denoise = None
+    if a.temporal_denoise is not None:                                   # as the ratio filter: one per run
+        from fdn_hip.mctf import TemporalDenoiser
+        denoise = TemporalDenoiser(h, w, fmt, a.temporal_denoise, a.denoise_threshold, a.denoise_radius, a.denoise_cut, device=dev)
+
     def enhance(frames):
         return enhance_yuv420(net, lp, frames, h, w, fmt, ratio_mode=a.model, tile=a.tile, ratio_from=a.tile_ratio, overlap=a.tile_overlap,
-                              batch=a.batch, blend=a.tile_blend, temporal=smooth)
+                              batch=a.batch, blend=a.tile_blend, temporal=smooth, denoise=denoise)
 
     try:
         done = stream_video(a, reader, dst, fmt, w, h, y4m_line, enhance, dev)
