@@ -13,7 +13,7 @@ mkdir -p fdn_hip "$BUILD"
 # VALU-issue-bound kernels listed here measure faster without it (fdffn_mid 2.35 -> 1.89 ms at level 1).
 NOSLP="patchfft ffn_tail fdsa_full"
 OBJS=""
-SEPARATE="correct sharpness fusion motion mctf"                     # linked into $(dirname $OUT)/libfdn_<name>.so, not into $OUT
+SEPARATE="correct sharpness fusion motion mctf msssim"                   # linked into $(dirname $OUT)/libfdn_<name>.so, not into $OUT
 PIDS=""
 NEWEST_HDR=$(ls -t csrc/*.hpp csrc/*.inc ../include/*.h build.sh | head -1)
 for f in csrc/*.hip; do

@@ -7,6 +7,7 @@ own reader, and no detour through 8-bit RGB, so 10 bit is scored as 10 bit.  No 
     ffmpeg -i out.mp4 -f yuv4mpegpipe -strict -1 - | python calculate_video_metrics.py --ref gt.y4m -
     python calculate_video_metrics.py --size 1280x720 --pix-fmt nv12 enhanced.yuv          # no ground truth: mean luma, cuts, flicker
     python calculate_video_metrics.py --ref gt.y4m enhanced.y4m --motion --motion-radius 12   # and the motion-compensated figures
+    python calculate_video_metrics.py --ref gt.y4m enhanced.y4m --ms-ssim                     # and multi-scale SSIM on luma
 
 REF and DIST are paths, DIST may be `-` for stdin.  PSNR is on the codes (peak 2^bits - 1) whatever the range of the stream, the `average`
 pools the three planes as ffmpeg's psnr filter does; SSIM is the reference's _ssim_cly on the luma codes; mean_y and dmean (the change of
@@ -17,7 +18,10 @@ DIST itself without one, which flatters it) by full search over +-N pixels (--mo
 the previous output frame predicts this one; `ref`: the same on REF, the ceiling), tc (the RMS difference of DIST's compensated change
 against REF's, 8-bit code units: the local counterpart of the flicker figure) and the share of moving blocks; `-` at a scene cut.  Each
 frame line, the CSV (mc_psnr, mc_psnr_ref, tc_rmse, moving, mean_mv) and one line `temporal:` after `flicker:` carry them; without
---motion stdout and the CSV are what they were.  Streams of
+--motion stdout and the CSV are what they were.
+--ms-ssim (needs --ref) adds the multi-scale SSIM of the luma planes (fdn_hip.msssim.MsSsimScore, libfdn_msssim.so; 10 bit scored as
+10 bit): `, MS-SSIM-Y x.xxxxxx` at the end of each frame line and of the `Average:` line, and a last CSV column ms_ssim_y.  Five scales
+need frames of at least 161x161; a smaller stream is refused.  Without --ms-ssim stdout and the CSV are what they were.  Streams of
 unequal length: the common prefix is scored, both lengths are named and the exit status is 1.  One process, one GPU; needs a ROCm GPU
 and the built libfdn_hip.so, there is no CPU fallback.
 """
@@ -31,6 +35,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from inference_fdn_video import SAMPLE_BYTES, open_video, say, size_arg, unit_fraction  # noqa: E402
 
 ME = "calculate_video_metrics.py"
+MS_SSIM_COLUMNS = ("ms_ssim_y",)                                                # after every other column, with --ms-ssim
+MS_SSIM_MIN_SIDE = 161                                                          # FDN_MSSSIM_MIN_SIDE of include/fdn_msssim.h
 MOTION_COLUMNS = ("mc_psnr", "mc_psnr_ref", "tc_rmse", "moving", "mean_mv")     # after CSV_COLUMNS, with --motion
 CSV_COLUMNS = ("frame", "psnr_y", "psnr_u", "psnr_v", "psnr_avg", "ssim_y", "mean_y_ref", "mean_y", "cut", "dmean_ref", "dmean")
 
@@ -50,6 +56,7 @@ def parse_args(argv=None):
     ap.add_argument("--motion", action="store_true",
                     help="add the motion-compensated temporal consistency: mc-PSNR, tc, moving blocks (vectors from REF, else from DIST)")
     ap.add_argument("--motion-radius", type=int, default=None, metavar="N", help="search +-N pixels around every 16 x 16 block, 0 .. 16 (default 8)")
+    ap.add_argument("--ms-ssim", action="store_true", help="add the multi-scale SSIM of the luma planes against REF (frames of at least 161x161)")
     ap.add_argument("--csv", default=None, metavar="PATH", help="write the per-frame records there, floats as repr() writes them")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
@@ -61,6 +68,8 @@ def parse_args(argv=None):
         a.motion_radius = 8
     if not 0 <= a.motion_radius <= 16:
         ap.error("--motion-radius must be in 0 .. 16")
+    if a.ms_ssim and a.ref is None:
+        ap.error("--ms-ssim needs --ref: the score is of a pair")
     if a.ref == "-":
         ap.error("REF is a path: only DIST may be stdin")
     return a
@@ -127,6 +136,11 @@ def motion_part(m, has_ref):
     return f", mc-PSNR {_num(m['mc_psnr'], '.4f')}{ref}{tc}, moving {_num(m['moving'], '.3f')}"
 
 
+def ms_ssim_part(ms):
+    """what --ms-ssim adds to a frame line and to the `Average:` line"""
+    return f", MS-SSIM-Y {ms['ms_ssim_y']:.6f}"
+
+
 def motion_cells(m):
     return ",".join("" if m[k] is None else repr(float(m[k])) for k in MOTION_COLUMNS)
 
@@ -149,6 +163,8 @@ def main(argv=None):
     a = parse_args(argv)
     dist, ref, fmt, w, h = open_pair(a)
     try:
+        if a.ms_ssim and (w < MS_SSIM_MIN_SIDE or h < MS_SSIM_MIN_SIDE):
+            raise SystemExit(f"{ME}: --ms-ssim: five scales need frames of at least {MS_SSIM_MIN_SIDE}x{MS_SSIM_MIN_SIDE}, the streams are {w}x{h}")
         score_streams(a, dist, ref, fmt, w, h)
     finally:
         close_streams(dist, ref)
@@ -167,13 +183,17 @@ def score_streams(a, dist, ref, fmt, w, h):
     if a.motion:
         from fdn_hip.motion import MotionScore
         motion = MotionScore(h, w, fmt, radius=a.motion_radius, device=dev)
+    msssim = None
+    if a.ms_ssim:
+        from fdn_hip.msssim import MsSsimScore
+        msssim = MsSsimScore(h, w, fmt, device=dev)
     n = fmt.frame_samples(h, w)
     as_bytes = lambda t: t.numpy().view(np.uint8).reshape(a.batch, -1)  # noqa: E731
     buf_d = torch.empty((a.batch, n), dtype=fmt.dtype)
     buf_r = torch.empty((a.batch, n), dtype=fmt.dtype) if ref is not None else None
     out = open(a.csv, "w") if a.csv else None
     if out:
-        out.write(",".join(CSV_COLUMNS + (MOTION_COLUMNS if motion else ())) + "\n")
+        out.write(",".join(CSV_COLUMNS + (MOTION_COLUMNS if motion else ()) + (MS_SSIM_COLUMNS if msssim else ())) + "\n")
     done = 0
     try:
         while True:
@@ -184,10 +204,11 @@ def score_streams(a, dist, ref, fmt, w, h):
                 on_d, on_r = buf_d[:k].to(dev), (None if ref is None else buf_r[:k].to(dev))
                 recs = score.update(on_d, on_r)
                 mrecs = motion.update(on_d, on_r, cuts=[r["cut"] for r in recs]) if motion else [None] * k
-                for r, m in zip(recs, mrecs):
-                    print(frame_line(done, r, ref is not None) + (motion_part(m, ref is not None) if motion else ""))
+                srecs = msssim.update(on_d, on_r) if msssim else [None] * k
+                for r, m, ms in zip(recs, mrecs, srecs):
+                    print(frame_line(done, r, ref is not None) + (motion_part(m, ref is not None) if motion else "") + (ms_ssim_part(ms) if msssim else ""))
                     if out:
-                        out.write(csv_row(done, r) + ("," + motion_cells(m) if motion else "") + "\n")
+                        out.write(csv_row(done, r) + ("," + motion_cells(m) if motion else "") + ("," + repr(ms["ms_ssim_y"]) if msssim else "") + "\n")
                     done += 1
             if nd < a.batch or nr < a.batch:
                 break
@@ -201,7 +222,7 @@ def score_streams(a, dist, ref, fmt, w, h):
         if ref is not None:
             print(f"Average: PSNR y {s['psnr_y']:.4f} u {s['psnr_u']:.4f} v {s['psnr_v']:.4f} avg {s['psnr_avg']:.4f} dB (over the stream: y "
                   f"{s['psnr_y_global']:.4f} avg {s['psnr_avg_global']:.4f} dB), SSIM-Y {s['ssim_y']:.6f}, mean_y {s['mean_y']:.3f} "
-                  f"(ref {s['mean_y_ref']:.3f}), {s['cuts']} scene cuts in {done} frames")
+                  f"(ref {s['mean_y_ref']:.3f}), {s['cuts']} scene cuts in {done} frames" + (ms_ssim_part(msssim.summary()) if msssim else ""))
         else:
             print(f"Average: mean_y {s['mean_y']:.3f}, {s['cuts']} scene cuts in {done} frames")
         if s["flicker"] == s["flicker"]:                                  # not nan: some frame followed a frame of its scene

@@ -29,6 +29,8 @@ what the two mean): a wrong ratio costs the plain scores and not these.  A frame
 stderr and the exit status is 1.  --sharpness appends the three deblurring figures of fdn_hip.sharpness (calculate_sharpness_metrics.py has what
 they mean): edge, the reference's EdgeLoss of the restored frame against the ground truth, gmsd, and grad_ratio, the mean gradient
 magnitude of the restored frame over that of the ground truth (below 1: softer than the truth), from the whole 8-bit frames.
+--ms-ssim appends the multi-scale SSIM of fdn_hip.msssim (calculate_ms_ssim.py has what it means): the mean over R, G and B of the
+five-scale score of the whole restored 8-bit frame against the ground truth; frames below 161 pixels in either side are refused.
 """
 import argparse
 import glob
@@ -105,6 +107,8 @@ def parse_args(argv=None):
                     help="also score every frame after a brightness correction towards the ground truth (fdn_hip.correct)")
     ap.add_argument("--sharpness", action="store_true", default=argparse.SUPPRESS,
                     help="also score the edge error, GMSD and the mean-gradient ratio against the ground truth (fdn_hip.sharpness)")
+    ap.add_argument("--ms-ssim", action="store_true", default=argparse.SUPPRESS,
+                    help="also score the multi-scale SSIM (rgb) against the ground truth (fdn_hip.msssim; frames of at least 161x161)")
     a = ap.parse_args(glue_bracket(argv))
     if not 1 <= a.fourier_bands <= 32:
         ap.error("--fourier-bands must be in 1 .. 32")
@@ -133,7 +137,7 @@ def csv_header(a):
         from fdn_hip import spectral
         cols += "," + ",".join(spectral.csv_header(a.fourier_bands))
     return cols + (",loe,deltae" if getattr(a, "lowlight", False) else "") + (",psnr_corr,ssim_corr" if getattr(a, "correct", None) else "") + (
-        ",edge,gmsd,grad_ratio" if getattr(a, "sharpness", False) else "")
+        ",edge,gmsd,grad_ratio" if getattr(a, "sharpness", False) else "") + (",ms_ssim" if getattr(a, "ms_ssim", False) else "")
 
 
 def main(argv=None):
@@ -161,6 +165,9 @@ def main(argv=None):
     if want_sh:
         from calculate_sharpness_metrics import sharpness_line
         from fdn_hip import FdnHipError, sharpness
+    want_ms = getattr(a, "ms_ssim", False)
+    if want_ms:
+        from fdn_hip import FdnHipError, msssim
 
     dev = torch.device(a.device)
     torch.cuda.set_device(dev)
@@ -178,6 +185,7 @@ def main(argv=None):
 
     n = len(a.pairs)
     psnr, ssim, ratio, fourier, ll, corr, sh = [None] * n, [None] * n, [None] * n, [None] * n, [None] * n, [None] * n, [None] * n
+    mss = [None] * n
     with ThreadPoolExecutor(max_workers=4) as pool:
         writers = []
         for idx, lqs, gts in decoded_groups(a.pairs, a.batch, pool):
@@ -205,6 +213,11 @@ def main(argv=None):
                     sm = sharpness.sharpness_metrics(gt, out, bgr=False)
                 except FdnHipError as e:
                     sys.exit(f"validate_fdn.py: --sharpness: {e}")
+            if want_ms:
+                try:
+                    mm = msssim.ms_ssim_u8(gt, out, mode="rgb", bgr=False)
+                except FdnHipError as e:
+                    sys.exit(f"validate_fdn.py: --ms-ssim: {e}")
             for k, i in enumerate(idx):
                 psnr[i], ssim[i], ratio[i] = p[k], s[k], r[k]
                 if a.fourier:
@@ -215,6 +228,8 @@ def main(argv=None):
                     corr[i] = (pc[0][k], pc[1][k])
                 if want_sh:
                     sh[i] = sm[k]
+                if want_ms:
+                    mss[i] = mm[k]["ms_ssim"]
                 if a.dest:
                     writers.append(pool.submit(write_rgb, a.dest[i], frames[k]))
         for w in writers:
@@ -225,11 +240,13 @@ def main(argv=None):
         tail += f", \t{lowlight_line(ll[i])}" if want_ll else ""
         tail += f", \t{mode_corr} PSNR: {corr[i][0]:.6f} dB, \t{mode_corr} SSIM: {corr[i][1]:.6f}" if mode_corr else ""
         tail += f", \t{sharpness_line(sh[i])}" if want_sh else ""
+        tail += f", \tMS-SSIM: {mss[i]:.6f}" if want_ms else ""
         print(f'{i+1:3d}: {basename:25}. \tPSNR: {psnr[i]:.6f} dB, \tSSIM: {ssim[i]:.6f}{tail}')
     tail = ", " + fourier_line({k: mean_of([m[k] for m in fourier]) for k in SUMMARY_KEYS}) if a.fourier else ""
     tail += ", " + lowlight_line({k: sum(m[k] for m in ll) / n for k in ("loe", "deltae")}) if want_ll else ""
     tail += f", {mode_corr} PSNR: {sum(c[0] for c in corr) / n:.6f} dB, {mode_corr} SSIM: {sum(c[1] for c in corr) / n:.6f}" if mode_corr else ""
     tail += ", " + sharpness_line({k: sum(m[k] for m in sh) / n for k in ("edge", "gmsd", "grad_ratio")}) if want_sh else ""
+    tail += f", MS-SSIM: {sum(mss) / n:.6f}" if want_ms else ""
     print(f'Average: PSNR: {sum(psnr) / n:.6f} dB, SSIM: {sum(ssim) / n:.6f}{tail}')
     if a.csv:
         os.makedirs(os.path.dirname(a.csv) or ".", exist_ok=True)
@@ -240,6 +257,7 @@ def main(argv=None):
                 tail += f",{ll[i]['loe']!r},{ll[i]['deltae']!r}" if want_ll else ""
                 tail += f",{corr[i][0]!r},{corr[i][1]!r}" if mode_corr else ""
                 tail += f",{sh[i]['edge']!r},{sh[i]['gmsd']!r},{sh[i]['grad_ratio']!r}" if want_sh else ""
+                tail += f",{mss[i]!r}" if want_ms else ""
                 f.write(f"{lq_path},{p!r},{s!r},{';'.join(repr(v) for v in r)}{tail}\n")
     if a.dest:
         print(f"{n} frames -> {a.output}")
