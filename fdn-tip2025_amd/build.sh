@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build libfdn_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU): every csrc/*.hip, one shared object - but for the files of
 # SEPARATE, each linked into a library of its own beside it (csrc/correct.hip -> libfdn_correct.so, which fdn_hip/correct.py loads itself, and
-# csrc/sharpness.hip -> libfdn_sharpness.so for fdn_hip/sharpness.py, csrc/fusion.hip -> libfdn_fusion.so for fdn_hip/fusion.py, csrc/motion.hip -> libfdn_motion.so for fdn_hip/motion.py, csrc/mctf.hip -> libfdn_mctf.so for fdn_hip/mctf.py; libfdn_hip.so does not depend on them, and its own code objects, the
+# csrc/sharpness.hip -> libfdn_sharpness.so for fdn_hip/sharpness.py, csrc/fusion.hip -> libfdn_fusion.so for fdn_hip/fusion.py, csrc/motion.hip -> libfdn_motion.so for fdn_hip/motion.py, csrc/mctf.hip -> libfdn_mctf.so for fdn_hip/mctf.py, csrc/piqe.hip -> libfdn_piqe.so for fdn_hip/piqe.py; libfdn_hip.so does not depend on them, and its own code objects, the
 # subject of tests/kernel_table.txt, stay what they were).
 #   OUT=path BUILD=dir EXTRA="flags" ./build.sh   builds a variant elsewhere (A/B experiments)
 set -e
@@ -13,7 +13,7 @@ mkdir -p fdn_hip "$BUILD"
 # VALU-issue-bound kernels listed here measure faster without it (fdffn_mid 2.35 -> 1.89 ms at level 1).
 NOSLP="patchfft ffn_tail fdsa_full"
 OBJS=""
-SEPARATE="correct sharpness fusion motion mctf msssim"                   # linked into $(dirname $OUT)/libfdn_<name>.so, not into $OUT
+SEPARATE="correct sharpness fusion motion mctf msssim piqe"                   # linked into $(dirname $OUT)/libfdn_<name>.so, not into $OUT
 PIDS=""
 NEWEST_HDR=$(ls -t csrc/*.hpp csrc/*.inc ../include/*.h build.sh | head -1)
 for f in csrc/*.hip; do

@@ -8,6 +8,7 @@ own reader, and no detour through 8-bit RGB, so 10 bit is scored as 10 bit.  No 
     python calculate_video_metrics.py --size 1280x720 --pix-fmt nv12 enhanced.yuv          # no ground truth: mean luma, cuts, flicker
     python calculate_video_metrics.py --ref gt.y4m enhanced.y4m --motion --motion-radius 12   # and the motion-compensated figures
     python calculate_video_metrics.py --ref gt.y4m enhanced.y4m --ms-ssim                     # and multi-scale SSIM on luma
+    python calculate_video_metrics.py enhanced.y4m --piqe                                     # no ground truth: and PIQE on luma
 
 REF and DIST are paths, DIST may be `-` for stdin.  PSNR is on the codes (peak 2^bits - 1) whatever the range of the stream, the `average`
 pools the three planes as ffmpeg's psnr filter does; SSIM is the reference's _ssim_cly on the luma codes; mean_y and dmean (the change of
@@ -21,7 +22,11 @@ frame line, the CSV (mc_psnr, mc_psnr_ref, tc_rmse, moving, mean_mv) and one lin
 --motion stdout and the CSV are what they were.
 --ms-ssim (needs --ref) adds the multi-scale SSIM of the luma planes (fdn_hip.msssim.MsSsimScore, libfdn_msssim.so; 10 bit scored as
 10 bit): `, MS-SSIM-Y x.xxxxxx` at the end of each frame line and of the `Average:` line, and a last CSV column ms_ssim_y.  Five scales
-need frames of at least 161x161; a smaller stream is refused.  Without --ms-ssim stdout and the CSV are what they were.  Streams of
+need frames of at least 161x161; a smaller stream is refused.  Without --ms-ssim stdout and the CSV are what they were.
+--piqe adds the no-reference PIQE of DIST's luma planes (fdn_hip.piqe.PiqeScore, libfdn_piqe.so; 0 best, 100 worst, exactly 100 for a
+flat frame; 10-bit codes count as quarters of an 8-bit code) and with --ref that of REF's beside it: `, PIQE-Y x.xxxxxx` (`(ref
+x.xxxxxx)`) at the very end of each frame line and of the `Average:` line, and the last CSV columns piqe_y (and piqe_y_ref).  It works
+without --ref.  Without --piqe stdout and the CSV are what they were.  Streams of
 unequal length: the common prefix is scored, both lengths are named and the exit status is 1.  One process, one GPU; needs a ROCm GPU
 and the built libfdn_hip.so, there is no CPU fallback.
 """
@@ -35,6 +40,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from inference_fdn_video import SAMPLE_BYTES, open_video, say, size_arg, unit_fraction  # noqa: E402
 
 ME = "calculate_video_metrics.py"
+PIQE_COLUMNS = ("piqe_y", "piqe_y_ref")                                          # the very last columns, with --piqe; the second with --ref
 MS_SSIM_COLUMNS = ("ms_ssim_y",)                                                # after every other column, with --ms-ssim
 MS_SSIM_MIN_SIDE = 161                                                          # FDN_MSSSIM_MIN_SIDE of include/fdn_msssim.h
 MOTION_COLUMNS = ("mc_psnr", "mc_psnr_ref", "tc_rmse", "moving", "mean_mv")     # after CSV_COLUMNS, with --motion
@@ -57,6 +63,7 @@ def parse_args(argv=None):
                     help="add the motion-compensated temporal consistency: mc-PSNR, tc, moving blocks (vectors from REF, else from DIST)")
     ap.add_argument("--motion-radius", type=int, default=None, metavar="N", help="search +-N pixels around every 16 x 16 block, 0 .. 16 (default 8)")
     ap.add_argument("--ms-ssim", action="store_true", help="add the multi-scale SSIM of the luma planes against REF (frames of at least 161x161)")
+    ap.add_argument("--piqe", action="store_true", help="add the no-reference PIQE of the luma planes of DIST (and of REF, when given)")
     ap.add_argument("--csv", default=None, metavar="PATH", help="write the per-frame records there, floats as repr() writes them")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
@@ -141,6 +148,11 @@ def ms_ssim_part(ms):
     return f", MS-SSIM-Y {ms['ms_ssim_y']:.6f}"
 
 
+def piqe_part(p, pr=None):
+    """what --piqe adds to a frame line and to the `Average:` line; pr: the record of REF, when there is one"""
+    return f", PIQE-Y {p['piqe_y']:.6f}" + (f" (ref {pr['piqe_y']:.6f})" if pr is not None else "")
+
+
 def motion_cells(m):
     return ",".join("" if m[k] is None else repr(float(m[k])) for k in MOTION_COLUMNS)
 
@@ -187,13 +199,19 @@ def score_streams(a, dist, ref, fmt, w, h):
     if a.ms_ssim:
         from fdn_hip.msssim import MsSsimScore
         msssim = MsSsimScore(h, w, fmt, device=dev)
+    piqe = piqe_ref = None
+    if a.piqe:
+        from fdn_hip.piqe import PiqeScore
+        piqe = PiqeScore(h, w, fmt, device=dev)
+        piqe_ref = PiqeScore(h, w, fmt, device=dev) if ref is not None else None
     n = fmt.frame_samples(h, w)
     as_bytes = lambda t: t.numpy().view(np.uint8).reshape(a.batch, -1)  # noqa: E731
     buf_d = torch.empty((a.batch, n), dtype=fmt.dtype)
     buf_r = torch.empty((a.batch, n), dtype=fmt.dtype) if ref is not None else None
     out = open(a.csv, "w") if a.csv else None
     if out:
-        out.write(",".join(CSV_COLUMNS + (MOTION_COLUMNS if motion else ()) + (MS_SSIM_COLUMNS if msssim else ())) + "\n")
+        out.write(",".join(CSV_COLUMNS + (MOTION_COLUMNS if motion else ()) + (MS_SSIM_COLUMNS if msssim else ())
+                           + (PIQE_COLUMNS[:2 if piqe_ref else 1] if piqe else ())) + "\n")
     done = 0
     try:
         while True:
@@ -205,10 +223,14 @@ def score_streams(a, dist, ref, fmt, w, h):
                 recs = score.update(on_d, on_r)
                 mrecs = motion.update(on_d, on_r, cuts=[r["cut"] for r in recs]) if motion else [None] * k
                 srecs = msssim.update(on_d, on_r) if msssim else [None] * k
-                for r, m, ms in zip(recs, mrecs, srecs):
-                    print(frame_line(done, r, ref is not None) + (motion_part(m, ref is not None) if motion else "") + (ms_ssim_part(ms) if msssim else ""))
+                precs = piqe.update(on_d) if piqe else [None] * k
+                prrecs = piqe_ref.update(on_r) if piqe_ref else [None] * k
+                for r, m, ms, pq, pr in zip(recs, mrecs, srecs, precs, prrecs):
+                    print(frame_line(done, r, ref is not None) + (motion_part(m, ref is not None) if motion else "") + (ms_ssim_part(ms) if msssim else "")
+                          + (piqe_part(pq, pr) if piqe else ""))
                     if out:
-                        out.write(csv_row(done, r) + ("," + motion_cells(m) if motion else "") + ("," + repr(ms["ms_ssim_y"]) if msssim else "") + "\n")
+                        out.write(csv_row(done, r) + ("," + motion_cells(m) if motion else "") + ("," + repr(ms["ms_ssim_y"]) if msssim else "")
+                                  + ("," + repr(pq["piqe_y"]) + ("," + repr(pr["piqe_y"]) if pr is not None else "") if piqe else "") + "\n")
                     done += 1
             if nd < a.batch or nr < a.batch:
                 break
@@ -218,13 +240,14 @@ def score_streams(a, dist, ref, fmt, w, h):
         if out:
             out.close()
     s = score.summary()
+    ptail = piqe_part(piqe.summary(), piqe_ref.summary() if piqe_ref else None) if piqe else ""
     if done:
         if ref is not None:
             print(f"Average: PSNR y {s['psnr_y']:.4f} u {s['psnr_u']:.4f} v {s['psnr_v']:.4f} avg {s['psnr_avg']:.4f} dB (over the stream: y "
                   f"{s['psnr_y_global']:.4f} avg {s['psnr_avg_global']:.4f} dB), SSIM-Y {s['ssim_y']:.6f}, mean_y {s['mean_y']:.3f} "
-                  f"(ref {s['mean_y_ref']:.3f}), {s['cuts']} scene cuts in {done} frames" + (ms_ssim_part(msssim.summary()) if msssim else ""))
+                  f"(ref {s['mean_y_ref']:.3f}), {s['cuts']} scene cuts in {done} frames" + (ms_ssim_part(msssim.summary()) if msssim else "") + ptail)
         else:
-            print(f"Average: mean_y {s['mean_y']:.3f}, {s['cuts']} scene cuts in {done} frames")
+            print(f"Average: mean_y {s['mean_y']:.3f}, {s['cuts']} scene cuts in {done} frames" + ptail)
         if s["flicker"] == s["flicker"]:                                  # not nan: some frame followed a frame of its scene
             print(f"flicker: {s['flicker']:.4f}" + (f" (ref {s['flicker_ref']:.4f}, against ref {s['flicker_err']:.4f})" if ref is not None else "")
                   + " mean |dmean|, 8-bit code units")

@@ -31,6 +31,8 @@ they mean): edge, the reference's EdgeLoss of the restored frame against the gro
 magnitude of the restored frame over that of the ground truth (below 1: softer than the truth), from the whole 8-bit frames.
 --ms-ssim appends the multi-scale SSIM of fdn_hip.msssim (calculate_ms_ssim.py has what it means): the mean over R, G and B of the
 five-scale score of the whole restored 8-bit frame against the ground truth; frames below 161 pixels in either side are refused.
+--piqe appends the no-reference PIQE of fdn_hip.piqe (calculate_piqe.py has what it means; 0 best, 100 worst) of the whole restored
+8-bit frame and, beside it, that of the ground truth, so that the two can be read side by side.
 """
 import argparse
 import glob
@@ -109,6 +111,8 @@ def parse_args(argv=None):
                     help="also score the edge error, GMSD and the mean-gradient ratio against the ground truth (fdn_hip.sharpness)")
     ap.add_argument("--ms-ssim", action="store_true", default=argparse.SUPPRESS,
                     help="also score the multi-scale SSIM (rgb) against the ground truth (fdn_hip.msssim; frames of at least 161x161)")
+    ap.add_argument("--piqe", action="store_true", default=argparse.SUPPRESS,
+                    help="also score the no-reference PIQE of the restored frame and of the ground truth (fdn_hip.piqe)")
     a = ap.parse_args(glue_bracket(argv))
     if not 1 <= a.fourier_bands <= 32:
         ap.error("--fourier-bands must be in 1 .. 32")
@@ -137,7 +141,8 @@ def csv_header(a):
         from fdn_hip import spectral
         cols += "," + ",".join(spectral.csv_header(a.fourier_bands))
     return cols + (",loe,deltae" if getattr(a, "lowlight", False) else "") + (",psnr_corr,ssim_corr" if getattr(a, "correct", None) else "") + (
-        ",edge,gmsd,grad_ratio" if getattr(a, "sharpness", False) else "") + (",ms_ssim" if getattr(a, "ms_ssim", False) else "")
+        ",edge,gmsd,grad_ratio" if getattr(a, "sharpness", False) else "") + (",ms_ssim" if getattr(a, "ms_ssim", False) else "") + (
+        ",piqe,piqe_gt" if getattr(a, "piqe", False) else "")
 
 
 def main(argv=None):
@@ -168,6 +173,9 @@ def main(argv=None):
     want_ms = getattr(a, "ms_ssim", False)
     if want_ms:
         from fdn_hip import FdnHipError, msssim
+    want_pq = getattr(a, "piqe", False)
+    if want_pq:
+        from fdn_hip import FdnHipError, piqe
 
     dev = torch.device(a.device)
     torch.cuda.set_device(dev)
@@ -185,7 +193,7 @@ def main(argv=None):
 
     n = len(a.pairs)
     psnr, ssim, ratio, fourier, ll, corr, sh = [None] * n, [None] * n, [None] * n, [None] * n, [None] * n, [None] * n, [None] * n
-    mss = [None] * n
+    mss, pq = [None] * n, [None] * n
     with ThreadPoolExecutor(max_workers=4) as pool:
         writers = []
         for idx, lqs, gts in decoded_groups(a.pairs, a.batch, pool):
@@ -218,6 +226,11 @@ def main(argv=None):
                     mm = msssim.ms_ssim_u8(gt, out, mode="rgb", bgr=False)
                 except FdnHipError as e:
                     sys.exit(f"validate_fdn.py: --ms-ssim: {e}")
+            if want_pq:
+                try:
+                    pm, pg = piqe.piqe_u8(out, bgr=False), piqe.piqe_u8(gt, bgr=False)
+                except FdnHipError as e:
+                    sys.exit(f"validate_fdn.py: --piqe: {e}")
             for k, i in enumerate(idx):
                 psnr[i], ssim[i], ratio[i] = p[k], s[k], r[k]
                 if a.fourier:
@@ -230,6 +243,8 @@ def main(argv=None):
                     sh[i] = sm[k]
                 if want_ms:
                     mss[i] = mm[k]["ms_ssim"]
+                if want_pq:
+                    pq[i] = (pm[k]["piqe"], pg[k]["piqe"])
                 if a.dest:
                     writers.append(pool.submit(write_rgb, a.dest[i], frames[k]))
         for w in writers:
@@ -241,12 +256,14 @@ def main(argv=None):
         tail += f", \t{mode_corr} PSNR: {corr[i][0]:.6f} dB, \t{mode_corr} SSIM: {corr[i][1]:.6f}" if mode_corr else ""
         tail += f", \t{sharpness_line(sh[i])}" if want_sh else ""
         tail += f", \tMS-SSIM: {mss[i]:.6f}" if want_ms else ""
+        tail += f", \tPIQE: {pq[i][0]:.6f} (gt {pq[i][1]:.6f})" if want_pq else ""
         print(f'{i+1:3d}: {basename:25}. \tPSNR: {psnr[i]:.6f} dB, \tSSIM: {ssim[i]:.6f}{tail}')
     tail = ", " + fourier_line({k: mean_of([m[k] for m in fourier]) for k in SUMMARY_KEYS}) if a.fourier else ""
     tail += ", " + lowlight_line({k: sum(m[k] for m in ll) / n for k in ("loe", "deltae")}) if want_ll else ""
     tail += f", {mode_corr} PSNR: {sum(c[0] for c in corr) / n:.6f} dB, {mode_corr} SSIM: {sum(c[1] for c in corr) / n:.6f}" if mode_corr else ""
     tail += ", " + sharpness_line({k: sum(m[k] for m in sh) / n for k in ("edge", "gmsd", "grad_ratio")}) if want_sh else ""
     tail += f", MS-SSIM: {sum(mss) / n:.6f}" if want_ms else ""
+    tail += f", PIQE: {sum(q[0] for q in pq) / n:.6f} (gt {sum(q[1] for q in pq) / n:.6f})" if want_pq else ""
     print(f'Average: PSNR: {sum(psnr) / n:.6f} dB, SSIM: {sum(ssim) / n:.6f}{tail}')
     if a.csv:
         os.makedirs(os.path.dirname(a.csv) or ".", exist_ok=True)
@@ -258,6 +275,7 @@ def main(argv=None):
                 tail += f",{corr[i][0]!r},{corr[i][1]!r}" if mode_corr else ""
                 tail += f",{sh[i]['edge']!r},{sh[i]['gmsd']!r},{sh[i]['grad_ratio']!r}" if want_sh else ""
                 tail += f",{mss[i]!r}" if want_ms else ""
+                tail += f",{pq[i][0]!r},{pq[i][1]!r}" if want_pq else ""
                 f.write(f"{lq_path},{p!r},{s!r},{';'.join(repr(v) for v in r)}{tail}\n")
     if a.dest:
         print(f"{n} frames -> {a.output}")
